@@ -3,8 +3,15 @@
 strong views, FixMatch-style consistency loss), bf16 activations with fp32
 accumulation / master weights, synthetic uint8 inputs resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed
+step computed (its loss record and the updated parameters) as DIR/<name>.npy.
+`--full` adds the measurements that take runs of their own after the timed
+region: the step-boundary gaps, the two roofline legs and the CPU baseline
+(`step_boundary`, `roofline`, `cpu_baseline`; null in a plain run).
 
 One step = GPU augment of 3 views (384 images) + weak forward (128, no grad,
 on a second stream) + train forward/backward (256; weight gradients on a
@@ -54,7 +61,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step (labelled + unlabelled)")
     ap.add_argument("--labeled", type=int, default=None, help="labelled images per GPU per step (default: batch / 2)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the step boundaries, the roofline legs and the CPU "
+                         "baseline (runs of their own; a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): loss.npy = its "
+                         "[total, L_l, L_u, mask count] record, params.npy = the parameters after its AdamW update "
+                         "(a fixed seeded sample of them where they exceed 48 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--serial-weak", action="store_true", help="run the weak forward on the main stream (A/B)")
     ap.add_argument("--arch", default="resnet18", choices=["resnet18", "resnet50"],
                     help="resnet50 + --image-size 512 --batch 128 = BASELINE config 5 (per GPU)")
@@ -342,7 +356,76 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = out.loss.cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
 
+    boundary, roofline, cpu, conv_flops = None, None, None, None
+    if args.full:
+        boundary, roofline, cpu, conv_flops = full_measurements(args, step, x_l, y_l, x_u, ops, resnet_mod,
+                                                                rank, world, Bl, S)
+    if rank == 0:
+        imgs = args.batch * world * args.steps
+        value = imgs / elapsed
+        res = {
+            "metric": "images/sec semi-supervised train step, 224x224 bs=256, 1/2/4/8 MI355X"
+                      if (args.arch, S, args.batch) == ("resnet18", 224, 256) else
+                      f"images/sec semi-supervised train step, {args.arch} {S}x{S} bs={args.batch}",
+            "value": round(value, 2),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": f"synthetic uint8 {S}x{S}x3 images resident in HBM, random-init {args.arch} (seed 42)",
+            "config": {"workload": f"semi_consistency_{args.arch}_{S}",
+                       "model": args.arch, "global_batch": args.batch * world, "per_gpu_batch": args.batch,
+                       "labeled_per_gpu": Bl, "unlabeled_per_gpu": Bu, "image_size": S,
+                       "parallelism": f"dp{world}", "tau": 0.7,
+                       "gflop_per_step_per_gpu": round(Bl * GFLOP_PER_IMG_TRAIN + Bu * (GFLOP_PER_IMG_FWD
+                                                                                        + GFLOP_PER_IMG_TRAIN), 1)
+                       if (args.arch, S) == ("resnet18", 224) else
+                       None if conv_flops is None else round(conv_flops / 1e9, 1)},
+            "full": args.full,
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+            "sclk": sclk.summary(),
+            "step_boundary": boundary,
+            "last_loss": [round(v, 5) for v in loss],
+        }
+        print(json.dumps(res))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, out, model, max_elems=12 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    .npy files: the step's loss record and the model state its AdamW update
+    left (parameters in named_parameters() order, BatchNorm running statistics
+    in named_buffers() order).  Called right after the timed region, before any
+    further step.  Parameters above 48 MB (ResNet-50) are written as a fixed
+    seeded sample of 12 Mi elements, so two builds write the same positions."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]).cpu()
+        bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+        stats = torch.cat(bufs).cpu() if bufs else torch.zeros(0)
+    if flat.numel() > max_elems:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(20))[:max_elems].sort().values
+        flat = flat[idx]
+    np.save(os.path.join(path, "loss.npy"), out.loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), flat.numpy())
+    np.save(os.path.join(path, "bn_running_stats.npy"), stats.numpy())
+
+
+def full_measurements(args, step, x_l, y_l, x_u, ops, resnet_mod, rank, world, Bl, S):
+    """--full: the measurements that take steps of their own after the timed
+    region.  Returns (step_boundary, roofline, cpu_baseline, conv FLOPs per step)."""
     # step boundaries (after the timed region, same replay path): events on the
     # launch stream at each step's start and end; the stream's idle time
     # between one step's last launch and the next step's first is the time the
@@ -428,62 +511,30 @@ def main():
                                                         f"{args.batch} take minutes per CPU step), rate per image"),
                "step_times_s": [round(t, 3) for t in c["step_times_s"]]}
 
-    if rank == 0:
-        imgs = args.batch * world * args.steps
-        value = imgs / elapsed
-        res = {
-            "metric": "images/sec semi-supervised train step, 224x224 bs=256, 1/2/4/8 MI355X"
-                      if (args.arch, S, args.batch) == ("resnet18", 224, 256) else
-                      f"images/sec semi-supervised train step, {args.arch} {S}x{S} bs={args.batch}",
-            "value": round(value, 2),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": f"synthetic uint8 {S}x{S}x3 images resident in HBM, random-init {args.arch} (seed 42)",
-            "config": {"workload": f"semi_consistency_{args.arch}_{S}",
-                       "model": args.arch, "global_batch": args.batch * world, "per_gpu_batch": args.batch,
-                       "labeled_per_gpu": Bl, "unlabeled_per_gpu": Bu, "image_size": S,
-                       "parallelism": f"dp{world}", "tau": 0.7,
-                       "gflop_per_step_per_gpu": round(Bl * GFLOP_PER_IMG_TRAIN + Bu * (GFLOP_PER_IMG_FWD
-                                                                                        + GFLOP_PER_IMG_TRAIN), 1)
-                       if (args.arch, S) == ("resnet18", 224) else round(conv_flops / 1e9, 1)},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_note": ("bytes per step for the same conv family, PMC FETCH_SIZE*2 + WRITE_SIZE "
-                                          f"(profiles/{traffic_src}; Infinity-Cache hits are counted)")
-                         if traffic_src else f"no committed PMC passes for workload '{workload_key}'",
-                         "kernel": "conv family: conv_glds / conv_halo / conv_stem_halo / conv_halo_wgrad / "
-                                   "conv_stem_bwd_wgrad (fwd+dgrad+wgrad, incl. wgrad slab reduce), "
-                                   f"{conv_launches} launches/step, {conv_flops / 1e12:.3f} TFLOP/step "
-                                   f"in {conv_ms:.3f} ms (single stream, every launch at its full-chip grid; "
-                                   "rocprofv3 of this leg: `python bench.py --profile-leg full`, "
-                                   "tools/roofline_from_trace.py)",
-                         "by_pass": by_pass,
-                         "frac_production": round(prod_achieved / peak, 4),
-                         "production": {"achieved": round(prod_achieved, 1), "ms": round(prod_ms, 3),
-                                        "note": "the same launches with the side-stream wgrads' grid budgets "
-                                                "the overlapped step runs (one workgroup per CU; half the CUs for "
-                                                "the layer-1 wgrad), still serialised on one stream: "
-                                                "`python bench.py --profile-leg production`"},
-                         "sol": {"frac": round(sol_s / meas_s, 4), "sol_ms": round(sol_s * 1e3, 3),
-                                 "algorithmic_bytes": conv_bytes, "hbm_peak_gbps": HBM_PEAK_BPS / 1e9,
-                                 "note": "sum over the same launches of max(FLOPs / MFMA peak, algorithmic bytes / "
-                                         "HBM peak) divided by their measured time: the fraction of each launch's "
-                                         "own roofline (HBM-bound below ~312 FLOP/B)"}},
-            "cpu_baseline": cpu,
-            "sclk": sclk.summary(),
-            "step_boundary": boundary,
-            "last_loss": [round(v, 5) for v in loss],
-        }
-        print(json.dumps(res))
-    if world > 1:
-        dist.destroy_process_group()
+    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic,
+                "traffic_note": ("bytes per step for the same conv family, PMC FETCH_SIZE*2 + WRITE_SIZE "
+                                 f"(profiles/{traffic_src}; Infinity-Cache hits are counted)")
+                if traffic_src else f"no committed PMC passes for workload '{workload_key}'",
+                "kernel": "conv family: conv_glds / conv_halo / conv_stem_halo / conv_halo_wgrad / "
+                          "conv_stem_bwd_wgrad (fwd+dgrad+wgrad, incl. wgrad slab reduce), "
+                          f"{conv_launches} launches/step, {conv_flops / 1e12:.3f} TFLOP/step "
+                          f"in {conv_ms:.3f} ms (single stream, every launch at its full-chip grid; "
+                          "rocprofv3 of this leg: `python bench.py --profile-leg full`, "
+                          "tools/roofline_from_trace.py)",
+                "by_pass": by_pass,
+                "frac_production": round(prod_achieved / peak, 4),
+                "production": {"achieved": round(prod_achieved, 1), "ms": round(prod_ms, 3),
+                               "note": "the same launches with the side-stream wgrads' grid budgets "
+                                       "the overlapped step runs (one workgroup per CU; half the CUs for "
+                                       "the layer-1 wgrad), still serialised on one stream: "
+                                       "`python bench.py --profile-leg production`"},
+                "sol": {"frac": round(sol_s / meas_s, 4), "sol_ms": round(sol_s * 1e3, 3),
+                        "algorithmic_bytes": conv_bytes, "hbm_peak_gbps": HBM_PEAK_BPS / 1e9,
+                        "note": "sum over the same launches of max(FLOPs / MFMA peak, algorithmic bytes / "
+                                "HBM peak) divided by their measured time: the fraction of each launch's "
+                                "own roofline (HBM-bound below ~312 FLOP/B)"}}
+    return boundary, roofline, cpu, conv_flops
 
 
 if __name__ == "__main__":

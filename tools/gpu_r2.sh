@@ -21,24 +21,24 @@ for st in "$@"; do
       ;;
     bench|bench:*)
       a=${st#bench}; a=${a#:}; nb=$((nb+1))
-      timeout -k 10 420 python bench.py $a > $out/bench$nb.log 2>&1 || { tail -20 $out/bench$nb.log; exit 1; }
+      timeout -k 10 420 python bench.py --full $a > $out/bench$nb.log 2>&1 || { tail -20 $out/bench$nb.log; exit 1; }
       tail -1 $out/bench$nb.log
       ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
-        python bench.py --steps 10 --warmup 5 --no-cpu-baseline > $out/trace.log 2>&1 || { tail -20 $out/trace.log; exit 1; }
+        python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $out/trace.log 2>&1 || { tail -20 $out/trace.log; exit 1; }
       tail -1 $out/trace.log
       ;;
     mfma)
       timeout -s KILL 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY \
         SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $out/mfma -o run -- \
-        python bench.py --steps 3 --warmup 3 --no-cpu-baseline > $out/mfma.log 2>&1 || { tail -20 $out/mfma.log; exit 1; }
+        python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline > $out/mfma.log 2>&1 || { tail -20 $out/mfma.log; exit 1; }
       tail -1 $out/mfma.log
       ;;
     fetch|write)
       c=FETCH_SIZE; [ $st = write ] && c=WRITE_SIZE
       timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $out/$c -o run -- \
-        python bench.py --steps 3 --warmup 3 --no-cpu-baseline > $out/$c.log 2>&1 || { tail -20 $out/$c.log; exit 1; }
+        python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline > $out/$c.log 2>&1 || { tail -20 $out/$c.log; exit 1; }
       tail -1 $out/$c.log
       ;;
     py:*)

@@ -11,5 +11,5 @@ rc=$?; echo "pytest rc $rc"; tail -3 $o/pytest.log
 timeout -k 10 300 python -u tools/vendor_ceiling.py > $o/vendor.log 2>&1 || { echo vendor failed; tail -20 $o/vendor.log; exit 1; }
 cat $o/vendor.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $o/prof -o vend -- python tools/vendor_ceiling.py --iters 5 > $o/vendor_prof.log 2>&1 || { echo vendor prof failed; tail -5 $o/vendor_prof.log; exit 1; }
-timeout -k 10 420 python bench.py > $o/bench.log 2>&1 || { echo bench failed; tail -5 $o/bench.log; exit 1; }
+timeout -k 10 420 python bench.py --full > $o/bench.log 2>&1 || { echo bench failed; tail -5 $o/bench.log; exit 1; }
 tail -1 $o/bench.log

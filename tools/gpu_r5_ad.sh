@@ -9,5 +9,5 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
   tests/test_gpu_stem_pool.py tests/test_gpu_c5.py tests/test_gpu_r50_geometry.py > $o/tests.log 2>&1 || { echo tests failed; tail -30 $o/tests.log; exit 1; }
 tail -1 $o/tests.log
 bash tools/ab_env.sh c5pool "SSIP_POOL_ROWS=0" "SSIP_POOL_ROWS=4" 2 --arch resnet50 --image-size 512 --batch 128 --steps 10 || exit 1
-timeout -k 10 900 python bench.py --arch resnet50 --image-size 512 --batch 128 > $o/c5.log 2>&1 || { tail -20 $o/c5.log; exit 1; }
+timeout -k 10 900 python bench.py --full --arch resnet50 --image-size 512 --batch 128 > $o/c5.log 2>&1 || { tail -20 $o/c5.log; exit 1; }
 tail -1 $o/c5.log | cut -c1-300

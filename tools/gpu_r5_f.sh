@@ -12,5 +12,5 @@ tail -2 $o/tests.log
 bash tools/ab_env.sh wbatch "SSIP_WGRAD_BATCH=0" "SSIP_WGRAD_BATCH=1" 3 || exit 1
 bash tools/ab_env.sh fin64 "SSIP_FIN64=0" "SSIP_FIN64=1" 3 || exit 1
 SSIP_FIN64=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $o/trace -o run -- \
-  python bench.py --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
+  python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
 echo done

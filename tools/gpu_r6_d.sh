@@ -7,7 +7,7 @@ mkdir -p $o
 (rocprofv3 -L 2>/dev/null || true) | grep -i -E "MFMA|COEXEC|WAIT_ANY|VALU_BUSY" | head -40 > $o/counters.txt
 cat $o/counters.txt
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $o/trace -o run -- \
-  python bench.py --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
+  python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
 f=$(ls $o/trace/*/run_kernel_trace.csv 2>/dev/null | head -1); [ -z "$f" ] && f=$(find $o/trace -name "*kernel_trace.csv" | head -1)
 python tools/step_families.py $f > $o/families.txt && head -45 $o/families.txt
 python tools/step_streams.py $f > $o/streams.txt && head -12 $o/streams.txt

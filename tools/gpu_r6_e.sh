@@ -12,7 +12,7 @@ bash tools/ab_env.sh r6e_c5 "SSIP_BNRELU_GLDS=0" "SSIP_BNRELU_GLDS=1" 2 --arch r
 bash tools/ab_env.sh r6e_r18 "SSIP_BNRELU_GLDS=1" "SSIP_BNRELU_GLDS=3" 3 || exit 1
 bash tools/ab_env.sh r6e_c5b "SSIP_BNRELU_GLDS=1" "SSIP_BNRELU_GLDS=3" 2 --arch resnet50 --image-size 512 --batch 128 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $o/trace -o run -- \
-  python bench.py --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
+  python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $o/trace.log 2>&1 || { tail -20 $o/trace.log; exit 1; }
 f=$(find $o/trace -name "*kernel_trace.csv" | head -1)
 python tools/step_families.py $f > $o/families.txt && head -50 $o/families.txt
 python tools/step_streams.py $f > $o/streams.txt && head -12 $o/streams.txt

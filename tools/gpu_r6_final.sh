@@ -3,5 +3,6 @@
 set -o pipefail
 export TMPDIR=/tmp
 bash tools/gpu_r6_full.sh r6final || exit 1
-timeout -k 10 500 python bench.py > gpurun_out/r6final/bench.log 2>&1 || { tail -20 gpurun_out/r6final/bench.log; exit 1; }
-tail -1 gpurun_out/r6final/bench.log | cut -c1-300
+o=$(dirname $(ls -d */r6final/tests.log))  # where gpu_r6_full.sh wrote its logs
+timeout -k 10 500 python bench.py --full > $o/bench.log 2>&1 || { tail -20 $o/bench.log; exit 1; }
+tail -1 $o/bench.log | cut -c1-300

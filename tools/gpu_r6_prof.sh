@@ -9,7 +9,7 @@ tag=${1:-r6prof}; shift
 extra=("$@")
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 300 python bench.py --no-cpu-baseline "${extra[@]}" > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline "${extra[@]}" > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
 tail -1 $out/bench.log | cut -c1-300
 # the step's conv-family TFLOP from the line itself (R18 3.1895, R50 512^2 18.975)
 tf=$(python3 -c "import json; print(json.loads(open('$out/bench.log').read().strip().splitlines()[-1])['config']['gflop_per_step_per_gpu'] / 1000)")
@@ -48,7 +48,7 @@ mhz2=$(python3 -c "import json; print(json.load(open('$out/sclk_mfma_production_
 python3 tools/pmc_mfma.py $f $out/mfma_busy_leg_production_s0.txt --sclk-mhz $mhz2 | head -12
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $out/$c -o run -- \
-    python bench.py --steps 3 --warmup 3 --no-cpu-baseline --exec eager "${extra[@]}" > $out/$c.log 2>&1 || { tail -20 $out/$c.log; exit 1; }
+    python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline --exec eager "${extra[@]}" > $out/$c.log 2>&1 || { tail -20 $out/$c.log; exit 1; }
 done
 du -sh $out
 echo "prof $tag done"

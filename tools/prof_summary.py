@@ -1,6 +1,6 @@
 """Summarise a rocprofv3 kernel trace (CSV): kernel time by family for one
 train step (the launches between two AdamW updates; default: the third
-from last, a timed graph-replayed step of bench.py).
+from last, a timed graph-replayed step of `bench.py --full`).
 
 usage: prof_summary.py run_kernel_trace.csv [step_index]
 """

@@ -1,5 +1,5 @@
 """Per-kernel-family device time per step (mean over three timed steps) by
-stream, from a rocprofv3 kernel trace of bench.py.
+stream, from a rocprofv3 kernel trace of `bench.py --full`.
 usage: step_families.py run_kernel_trace.csv [other_trace.csv]  (two: side by side)"""
 import collections
 import csv
