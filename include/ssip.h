@@ -23,6 +23,8 @@
  *     -> ssip_softmax_select
  *   (build extension, no reference) weak/strong consistency loss
  *     -> ssip_semi_loss
+ *   KMeans / DBSCAN / silhouette_score / kneighbors   src/clustering.py:330-438
+ *     -> ssip_kmeans_assign / _update, ssip_pairwise_eps / _kth / _cluster_sums
  *
  * Conventions
  *   - Every pointer is a device pointer unless documented otherwise; the
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define SSIP_ABI_VERSION 14
+#define SSIP_ABI_VERSION 15
 
 enum ssip_dtype { SSIP_F32 = 0, SSIP_BF16 = 1 };
 enum ssip_status { SSIP_OK = 0, SSIP_ERR_ARG = -1, SSIP_ERR_LAUNCH = -2, SSIP_ERR_WORKSPACE = -3 };
@@ -390,6 +392,45 @@ int ssip_weight_prep_batch(int dtype, int count, const ssip_wprep* items, void* 
  * ptrs is a HOST array of count <= SSIP_COUNTERS_MAX device pointers. */
 #define SSIP_COUNTERS_MAX 64
 int ssip_counters_add(int count, int64_t* const* ptrs, int64_t delta, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Embedding analytics (reference src/clustering.py:330-438: compute_silhouette
+ * :330-337, evaluate_kmeans :340-373, evaluate_dbscan :376-428,
+ * auto_eps_from_kdistance :430-438).  Points X are fp32 row-major [N][d],
+ * 1 <= d <= 512.  Every squared distance is sum_c (x_c - y_c)^2 in fp32, one
+ * fma per feature in feature order; no atomics, every reduction in a fixed
+ * order (bit-reproducible).
+ * ---------------------------------------------------------------------- */
+/* bytes of the Lloyd-iteration workspace: per-workgroup partial sums
+ * [G][K][d], counts [G][K], inertia [G] and changed-label counts [G] */
+int64_t ssip_kmeans_workspace_bytes(int64_t N, int d, int K);
+/* labels[i] = argmin_k |X[i] - centres[k]|^2 (a tie goes to the lowest k, as
+ * numpy.argmin), mind2[i] = that minimum; 2 <= K <= 64.  prev_labels
+ * (nullable = every label counts as changed) is the label vector the changed
+ * count is taken against; it must not alias labels.  The workspace (16-byte
+ * aligned) receives the partials ssip_kmeans_update reduces. */
+int ssip_kmeans_assign(int64_t N, int d, int K, const float* X, const float* centres, const int32_t* prev_labels,
+                       int32_t* labels, float* mind2, void* workspace, int64_t workspace_bytes, void* stream);
+/* Reduces the partials of the preceding ssip_kmeans_assign (same N, d, K) in
+ * workgroup order: new_centres[k] = mean of the points assigned to k,
+ * counts[k] = their number; an empty cluster keeps centres[k] and reports
+ * counts[k] = 0.  scalars (4 fp64): {sum |new_centres - centres|^2, inertia =
+ * sum mind2, number of changed labels, number of empty clusters}. */
+int ssip_kmeans_update(int64_t N, int d, int K, const void* workspace, int64_t workspace_bytes, const float* centres,
+                       float* new_centres, int32_t* counts, double* scalars, void* stream);
+/* X against itself under d2 <= eps^2: degree[i] = number of such j (self
+ * included), bitmap[i][j / 32] bit (j % 32) = the predicate, [N][ceil(N/32)]
+ * uint32 with zero padding bits.  N <= 65536 (512 MB of bitmap). */
+int ssip_pairwise_eps(int N, int d, const float* X, float eps, int32_t* degree, uint32_t* bitmap, void* stream);
+/* kth[i] = k-th smallest distance (not squared) from row i to any row, self
+ * included at 0: NearestNeighbors(n_neighbors=k).kneighbors(X)[0][:, -1].
+ * 1 <= k <= min(64, N). */
+int ssip_pairwise_kth(int N, int d, int k, const float* X, float* kth, void* stream);
+/* sums[i][c] = sum over the members j of cluster c of |X[i] - X[j]| (not
+ * squared), [N][K], K <= 256.  labels[N] in 0..K-1; order[N] = stable argsort
+ * of labels (host).  Columns are visited in `order`. */
+int ssip_pairwise_cluster_sums(int N, int d, int K, const float* X, const int32_t* labels, const int32_t* order,
+                               float* sums, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the stream-ordered entry points

@@ -1,0 +1,581 @@
+// Embedding analytics on the PCA cluster space: K-Means (Lloyd assign /
+// update), the DBSCAN eps-neighbourhood graph, the k-th neighbour distance
+// and the per-cluster distance sums behind the silhouette score.  These stand
+// in for the sklearn calls the reference makes at src/clustering.py:330-438
+// (KMeans.fit_predict, DBSCAN.fit_predict, silhouette_score,
+// NearestNeighbors.kneighbors).
+//
+// Points are fp32, row-major [N][d], 1 <= d <= 512.
+//
+// Every squared distance is the direct difference sum_c (x_c - y_c)^2,
+// accumulated in fp32 with one fma per feature in feature order, over
+// LDS-staged chunks of DC features.  The Gram form |x|^2 + |y|^2 - 2 x.y is
+// deliberately not used: every consumer here thresholds a distance or takes
+// an argmin that is compared with an fp64 oracle, the feature dimension is
+// small (5-60 for the PCA cluster space), and the Gram form's cancellation
+// error near d2 = 0 (self pairs, duplicates, eps thresholds) would buy
+// nothing.  The direct form also gives d2(i, j) == d2(j, i) and d2(i, i) == 0
+// bit for bit, so the eps graph is symmetric by construction.
+//
+// No atomics; every reduction runs in a fixed order, so all outputs are
+// bit-reproducible from run to run.  Two thread layouts:
+//   A (eps graph, k-th distance): a workgroup owns RA = 64 rows and walks all
+//     columns in tiles of 64; lane = column, each wave holds 16 rows, so one
+//     wave ballot is 64 columns of one row = two bitmap words.
+//   B (assign, cluster sums): a workgroup owns RB = 256 rows, thread = row,
+//     and walks the columns (centres / points in label order) in tiles of 16;
+//     everything that depends on the column is uniform across the workgroup.
+#include "ssip_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int DC = 32;        // features per LDS chunk
+constexpr int NT = 256;       // threads per workgroup (4 waves)
+constexpr int RA = 64;        // layout A: rows per workgroup (16 per wave)
+constexpr int XR_LD = 68;     // layout A: row-tile leading dimension ([DC][RA] transposed, 16-B aligned rows)
+constexpr int XC_LD = DC + 1; // +1 pad: lane-per-row reads hit 32 distinct banks
+constexpr int RB = 256;       // layout B: rows per workgroup
+constexpr int CT = 16;        // layout B: columns per tile
+constexpr int KMAX = 64;      // centres
+constexpr int UPD_NT = 1024;  // update: one workgroup
+
+// ---------------------------------------------------------------------------
+// layout A
+// ---------------------------------------------------------------------------
+// A 64 x DC tile is 8 elements per thread: element q of thread tid is (point
+// idx >> 5, feature idx & 31) with idx = tid + q * NT.  Tiles are fetched into
+// registers one step ahead of their use, so the global latency overlaps the
+// previous tile's arithmetic.
+constexpr int TQ = 64 * DC / NT;
+__device__ __forceinline__ void fetch_tile_a(float (&v)[TQ], const float* __restrict__ X, int p0, int N, int d, int c0,
+                                             int tid) {
+#pragma unroll
+  for (int q = 0; q < TQ; ++q) {
+    const int idx = tid + q * NT;
+    const int p = p0 + (idx >> 5), c = c0 + (idx & (DC - 1));
+    v[q] = (p < N && c < d) ? X[(long)p * d + c] : 0.f;
+  }
+}
+// xr[c][r] = X[row0 + r][c0 + c] (zero outside the matrix)
+__device__ __forceinline__ void put_rows_a(float* xr, const float (&v)[TQ], int tid) {
+#pragma unroll
+  for (int q = 0; q < TQ; ++q) {
+    const int idx = tid + q * NT;
+    xr[(idx & (DC - 1)) * XR_LD + (idx >> 5)] = v[q];
+  }
+}
+// xc[j][c] = X[col0 + j][c0 + c] (zero outside the matrix)
+__device__ __forceinline__ void put_cols_a(float* xc, const float (&v)[TQ], int tid) {
+#pragma unroll
+  for (int q = 0; q < TQ; ++q) {
+    const int idx = tid + q * NT;
+    xc[(idx >> 5) * XC_LD + (idx & (DC - 1))] = v[q];
+  }
+}
+// acc[u] += sum_c (x[row w*16+u][c] - x[col lane][c])^2 over one chunk
+__device__ __forceinline__ void accumulate_a(float (&acc)[16], const float* xr, const float* xc, int w, int lane) {
+#pragma unroll 4
+  for (int cc = 0; cc < DC; ++cc) {
+    const float cv = xc[lane * XC_LD + cc];
+    const f32x4* rp = reinterpret_cast<const f32x4*>(xr + cc * XR_LD + w * 16);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 rv = rp[q];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float df = rv[e] - cv;
+        acc[q * 4 + e] = fmaf(df, df, acc[q * 4 + e]);
+      }
+    }
+  }
+}
+
+// ascending bitonic sort of one value per lane across the wave
+__device__ __forceinline__ float wave_sort(float v, int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const float p = __shfl_xor(v, j, 64);
+      const bool up = (lane & k) == 0;
+      const bool lo = (lane & j) == 0;
+      v = (lo == up) ? fminf(v, p) : fmaxf(v, p);
+    }
+  }
+  return v;
+}
+// best: ascending 64 smallest so far; cand: 64 new values.  Returns the
+// ascending 64 smallest of the union.
+__device__ __forceinline__ float wave_merge_smallest(float best, float cand, int lane) {
+  const float s = wave_sort(cand, lane);
+  float m = fminf(best, __shfl(s, 63 - lane, 64));  // bitonic, holds the 64 smallest
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const float p = __shfl_xor(m, j, 64);
+    m = (lane & j) == 0 ? fminf(m, p) : fmaxf(m, p);
+  }
+  return m;
+}
+
+// MODE 0: degree + adjacency bitmap of d2 <= eps2.  MODE 1: k-th smallest distance.
+template <int MODE>
+__global__ __launch_bounds__(NT) void pairwise_a_kernel(int N, int d, const float* __restrict__ X, float eps2, int kk,
+                                                        int* __restrict__ degree, uint32_t* __restrict__ bitmap,
+                                                        float* __restrict__ kth) {
+  __shared__ __attribute__((aligned(16))) float xr[DC * XR_LD];
+  __shared__ float xc[64 * XC_LD];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int row0 = blockIdx.x * RA;
+  const int nch = (d + DC - 1) / DC, ntile = (N + 63) / 64;
+  const int W = (N + 31) / 32;
+
+  float best[16];
+  int deg[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    best[u] = INFINITY;
+    deg[u] = 0;
+  }
+
+  float pre_r[TQ], pre_c[TQ];
+  fetch_tile_a(pre_r, X, row0, N, d, 0, tid);
+  fetch_tile_a(pre_c, X, 0, N, d, 0, tid);
+  float acc[16];
+  const int steps = ntile * nch;
+  for (int it = 0; it < steps; ++it) {
+    const int jt = it / nch, ch = it - jt * nch;
+    // a single-chunk row tile stays resident for the whole column walk
+    if (nch > 1 || it == 0) put_rows_a(xr, pre_r, tid);
+    put_cols_a(xc, pre_c, tid);
+    __syncthreads();
+    if (it + 1 < steps) {  // next step's tiles, in flight during the arithmetic below
+      const int jn = (it + 1) / nch, cn = (it + 1) - jn * nch;
+      if (nch > 1) fetch_tile_a(pre_r, X, row0, N, d, cn * DC, tid);
+      fetch_tile_a(pre_c, X, jn * 64, N, d, cn * DC, tid);
+    }
+    if (ch == 0) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) acc[u] = 0.f;
+    }
+    accumulate_a(acc, xr, xc, w, lane);
+    __syncthreads();
+    if (ch != nch - 1) continue;
+    const int j = jt * 64 + lane;
+    if (MODE == 0) {
+      unsigned long long mine = 0;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int i = row0 + w * 16 + u;
+        const unsigned long long m = __ballot(j < N && i < N && acc[u] <= eps2);
+        deg[u] += __popcll(m);
+        if ((lane >> 1) == u) mine = m;
+      }
+      // lanes 0..31 store the wave's 16 rows x 2 words
+      const int i = row0 + w * 16 + (lane >> 1), wi = jt * 2 + (lane & 1);
+      if (lane < 32 && i < N && wi < W)
+        bitmap[(long)i * W + wi] = (uint32_t)((lane & 1) ? (mine >> 32) : (mine & 0xffffffffull));
+    } else {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const float cand = j < N ? acc[u] : INFINITY;
+        const float thr = __shfl(best[u], kk - 1, 64);
+        if (__any(cand < thr)) best[u] = wave_merge_smallest(best[u], cand, lane);  // wave-uniform branch
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int i = row0 + w * 16 + u;
+    if (MODE == 0) {
+      if (lane == u && i < N) degree[i] = deg[u];
+    } else {
+      const float v = __shfl(best[u], kk - 1, 64);
+      if (lane == u && i < N) kth[i] = sqrtf(v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// layout B
+// ---------------------------------------------------------------------------
+// xs[r][c] = X[row0 + r][c0 + c] (zero outside the matrix)
+__device__ __forceinline__ void stage_rows_b(float* xs, const float* __restrict__ X, long row0, long N, int d, int c0,
+                                             int tid) {
+  for (int idx = tid; idx < RB * DC; idx += NT) {
+    const int r = idx >> 5, cc = idx & (DC - 1);
+    const long row = row0 + r;
+    const int c = c0 + cc;
+    xs[r * XC_LD + cc] = (row < N && c < d) ? X[row * d + c] : 0.f;
+  }
+}
+// ys[c][u] = Y[col_s[u]][c0 + c] (zero for col_s[u] < 0 or outside d)
+__device__ __forceinline__ void stage_cols_b(float* ys, const float* __restrict__ Y, const int* col_s, int d, int c0,
+                                             int tid) {
+  for (int idx = tid; idx < CT * DC; idx += NT) {
+    const int u = idx >> 5, cc = idx & (DC - 1);
+    const int col = col_s[u], c = c0 + cc;
+    ys[cc * CT + u] = (col >= 0 && c < d) ? Y[(long)col * d + c] : 0.f;
+  }
+}
+__device__ __forceinline__ void accumulate_b(float (&acc)[CT], const float* xs, const float* ys, int tid) {
+#pragma unroll 4
+  for (int cc = 0; cc < DC; ++cc) {
+    const float xv = xs[tid * XC_LD + cc];
+    const f32x4* yp = reinterpret_cast<const f32x4*>(ys + cc * CT);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 yv = yp[q];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float df = xv - yv[e];
+        acc[q * 4 + e] = fmaf(df, df, acc[q * 4 + e]);
+      }
+    }
+  }
+}
+
+// Workspace of the Lloyd iteration, G = ceil(N / RB) workgroups.
+struct KmeansWs {
+  double* inertia;  // [G]
+  int* changed;     // [G]
+  int* counts;      // [G][K]
+  float* sums;      // [G][K][d]
+};
+inline long kmeans_groups(long N) { return (N + RB - 1) / RB; }
+inline long kmeans_ws_bytes(long N, int d, int K) {
+  const long G = kmeans_groups(N);
+  long b = G * 8 + G * 4 + G * K * 4;
+  b = (b + 15) / 16 * 16;
+  return b + G * K * d * 4;
+}
+inline KmeansWs kmeans_ws(void* base, long N, int d, int K) {
+  const long G = kmeans_groups(N);
+  char* p = static_cast<char*>(base);
+  KmeansWs ws;
+  ws.inertia = reinterpret_cast<double*>(p);
+  ws.changed = reinterpret_cast<int*>(p + G * 8);
+  ws.counts = reinterpret_cast<int*>(p + G * 8 + G * 4);
+  const long b = (G * 8 + G * 4 + G * K * 4 + 15) / 16 * 16;
+  ws.sums = reinterpret_cast<float*>(p + b);
+  return ws;
+}
+
+__global__ __launch_bounds__(NT) void kmeans_assign_kernel(long N, int d, int K, const float* __restrict__ X,
+                                                           const float* __restrict__ C, const int* __restrict__ prev,
+                                                           int* __restrict__ labels, float* __restrict__ mind2,
+                                                           KmeansWs ws) {
+  __shared__ float xs[RB * XC_LD];
+  __shared__ __attribute__((aligned(16))) float ys[DC * CT];
+  __shared__ int col_s[CT];
+  __shared__ int lab_s[RB];
+  __shared__ float red_f[NT / 64];
+  __shared__ int red_i[NT / 64];
+  const int tid = threadIdx.x;
+  const long row0 = (long)blockIdx.x * RB, row = row0 + tid;
+  const bool valid = row < N;
+  const int nch = (d + DC - 1) / DC;
+
+  float best = INFINITY;
+  int bi = 0;
+  for (int kt = 0; kt * CT < K; ++kt) {
+    __syncthreads();
+    if (tid < CT) col_s[tid] = kt * CT + tid < K ? kt * CT + tid : -1;
+    __syncthreads();
+    float acc[CT];
+#pragma unroll
+    for (int u = 0; u < CT; ++u) acc[u] = 0.f;
+    for (int ch = 0; ch < nch; ++ch) {
+      if (nch > 1 || kt == 0) stage_rows_b(xs, X, row0, N, d, ch * DC, tid);
+      stage_cols_b(ys, C, col_s, d, ch * DC, tid);
+      __syncthreads();
+      accumulate_b(acc, xs, ys, tid);
+      __syncthreads();
+    }
+    // strict <, centres in increasing index: a tie keeps the lowest index (numpy.argmin)
+#pragma unroll
+    for (int u = 0; u < CT; ++u) {
+      const int k = kt * CT + u;
+      if (k < K && acc[u] < best) {
+        best = acc[u];
+        bi = k;
+      }
+    }
+  }
+  int chg = 0;
+  if (valid) {
+    labels[row] = bi;
+    mind2[row] = best;
+    chg = prev == nullptr || prev[row] != bi;
+  }
+  lab_s[tid] = valid ? bi : -1;
+
+  // inertia and changed-label partials of this workgroup (butterfly within a
+  // wave, then the four waves in order)
+  const float ws_f = wave_sum(valid ? best : 0.f);
+  int ws_i = chg;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ws_i += __shfl_xor(ws_i, o, 64);
+  if ((tid & 63) == 0) {
+    red_f[tid >> 6] = ws_f;
+    red_i[tid >> 6] = ws_i;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    int c = 0;
+    for (int q = 0; q < NT / 64; ++q) {
+      s += (double)red_f[q];
+      c += red_i[q];
+    }
+    ws.inertia[blockIdx.x] = s;
+    ws.changed[blockIdx.x] = c;
+  }
+  if (tid < K) {
+    int c = 0;
+    for (int r = 0; r < RB; ++r) c += lab_s[r] == tid;
+    ws.counts[(long)blockIdx.x * K + tid] = c;
+  }
+
+  // per-cluster sums of this workgroup's points, rows in order.  Thread
+  // (c = feature of the chunk, g = tid / 32) owns clusters g, g + 8, ...
+  const int c = tid & (DC - 1), g = tid >> 5;
+  for (int ch = 0; ch < nch; ++ch) {
+    if (nch > 1) {
+      __syncthreads();
+      stage_rows_b(xs, X, row0, N, d, ch * DC, tid);
+      __syncthreads();
+    }
+    float a[KMAX / 8];
+#pragma unroll
+    for (int m = 0; m < KMAX / 8; ++m) a[m] = 0.f;
+    for (int r = 0; r < RB; ++r) {
+      const int l = lab_s[r];
+      if (l >= 0 && (l & 7) == g) {
+        const float x = xs[r * XC_LD + c];
+        const int mm = l >> 3;
+#pragma unroll
+        for (int m = 0; m < KMAX / 8; ++m) a[m] += (m == mm) ? x : 0.f;
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < KMAX / 8; ++m) {
+      const int k = g + 8 * m;
+      if (k < K && ch * DC + c < d) ws.sums[((long)blockIdx.x * K + k) * d + ch * DC + c] = a[m];
+    }
+  }
+}
+
+// One workgroup: reduce the G partials in index order (fp64), new centres,
+// counts and the scalars {sum |delta centre|^2, inertia, changed labels,
+// empty clusters}.
+__global__ __launch_bounds__(UPD_NT) void kmeans_update_kernel(long G, int d, int K, KmeansWs ws,
+                                                               const float* __restrict__ C, float* __restrict__ Cn,
+                                                               int* __restrict__ counts, double* __restrict__ scalars) {
+  __shared__ int cnt_s[KMAX];
+  __shared__ double red[3][UPD_NT];
+  const int tid = threadIdx.x;
+  if (tid < K) {
+    int c = 0;
+    for (long g = 0; g < G; ++g) c += ws.counts[g * K + tid];
+    cnt_s[tid] = c;
+    counts[tid] = c;
+  }
+  __syncthreads();
+  double shift = 0.0, inertia = 0.0, changed = 0.0;
+  for (int slot = tid; slot < K * d; slot += UPD_NT) {
+    const int k = slot / d;
+    double s = 0.0;
+    for (long g = 0; g < G; ++g) s += (double)ws.sums[g * K * d + slot];
+    const float old = C[slot];
+    const float nw = cnt_s[k] > 0 ? (float)(s / (double)cnt_s[k]) : old;  // an empty cluster keeps its centre
+    Cn[slot] = nw;
+    const double df = (double)nw - (double)old;
+    shift += df * df;
+  }
+  for (long g = tid; g < G; g += UPD_NT) {
+    inertia += ws.inertia[g];
+    changed += (double)ws.changed[g];
+  }
+  red[0][tid] = shift;
+  red[1][tid] = inertia;
+  red[2][tid] = changed;
+  __syncthreads();
+  for (int s = UPD_NT / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) red[q][tid] += red[q][tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    int empty = 0;
+    for (int k = 0; k < K; ++k) empty += cnt_s[k] == 0;
+    scalars[0] = red[0][0];
+    scalars[1] = red[1][0];
+    scalars[2] = red[2][0];
+    scalars[3] = (double)empty;
+  }
+}
+
+// sums[row][label] = sum of distances from the row to that cluster's members.
+// Columns come in label order, so each (row, label) slot is stored exactly
+// once, when the label of the walk changes (uniform across the workgroup).
+// Columns are staged SC = 64 at a time (four tiles of CT), which amortises the
+// order -> labels -> X chain of dependent loads and the barriers; the indices
+// of the next stage are fetched during the arithmetic of the current one.
+constexpr int SC = 64;
+__global__ __launch_bounds__(NT) void cluster_sums_kernel(int N, int d, int K, const float* __restrict__ X,
+                                                          const int* __restrict__ labels, const int* __restrict__ order,
+                                                          float* __restrict__ sums) {
+  __shared__ float xs[RB * XC_LD];
+  __shared__ __attribute__((aligned(16))) float ys[SC / CT][DC * CT];
+  __shared__ int col_s[SC];
+  __shared__ int lab_s[SC];
+  const int tid = threadIdx.x;
+  const long row0 = (long)blockIdx.x * RB, row = row0 + tid;
+  const int nch = (d + DC - 1) / DC;
+  float run = 0.f;
+  int cur = -1;
+
+  // (column, label) of stage position tid; -1 / -1 when it is not a member of any cluster
+  auto fetch_index = [&](int j, int& col, int& l) {
+    col = j < N ? order[j] : -1;
+    if (col < 0 || col >= N) col = -1;
+    l = col >= 0 ? labels[col] : -1;
+    if (l < 0 || l >= K) {
+      l = -1;
+      col = -1;
+    }
+  };
+  int ncol = -1, nlab = -1;
+  if (tid < SC) fetch_index(tid, ncol, nlab);
+
+  for (int j0 = 0; j0 < N; j0 += SC) {
+    __syncthreads();
+    if (tid < SC) {
+      col_s[tid] = ncol;
+      lab_s[tid] = nlab;
+    }
+    __syncthreads();
+    if (tid < SC) fetch_index(j0 + SC + tid, ncol, nlab);
+    float acc[SC];
+#pragma unroll
+    for (int u = 0; u < SC; ++u) acc[u] = 0.f;
+    for (int ch = 0; ch < nch; ++ch) {
+      if (nch > 1 || j0 == 0) stage_rows_b(xs, X, row0, N, d, ch * DC, tid);
+#pragma unroll
+      for (int t = 0; t < SC / CT; ++t) stage_cols_b(ys[t], X, col_s + t * CT, d, ch * DC, tid);
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < SC / CT; ++t) {
+        float a[CT];
+#pragma unroll
+        for (int u = 0; u < CT; ++u) a[u] = acc[t * CT + u];
+        accumulate_b(a, xs, ys[t], tid);
+#pragma unroll
+        for (int u = 0; u < CT; ++u) acc[t * CT + u] = a[u];
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < SC; ++u) {
+      const int l = lab_s[u];
+      if (l != cur) {
+        if (cur >= 0 && row < N) sums[row * K + cur] = run;
+        run = 0.f;
+        cur = l;
+      }
+      if (l >= 0) run += sqrtf(acc[u]);
+    }
+  }
+  if (cur >= 0 && row < N) sums[row * K + cur] = run;
+}
+
+int check_points(const char* what, long N, int d, const void* X) {
+  SSIP_REQUIRE(N >= 1, SSIP_ERR_ARG, "%s: N = %ld must be >= 1", what, N);
+  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "%s: d = %d outside 1..512", what, d);
+  SSIP_REQUIRE(X != nullptr, SSIP_ERR_ARG, "%s: null point matrix", what);
+  return SSIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ssip_kmeans_workspace_bytes(int64_t N, int d, int K) {
+  SSIP_REQUIRE(N >= 1 && d >= 1 && d <= 512 && K >= 2 && K <= KMAX, SSIP_ERR_ARG,
+               "ssip_kmeans_workspace_bytes: need N >= 1, 1 <= d <= 512, 2 <= K <= 64 (N=%ld d=%d K=%d)", (long)N, d,
+               K);
+  return kmeans_ws_bytes(N, d, K);
+}
+
+int ssip_kmeans_assign(int64_t N, int d, int K, const float* X, const float* centres, const int32_t* prev_labels,
+                       int32_t* labels, float* mind2, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_points("ssip_kmeans_assign", N, d, X)) return rc;
+  SSIP_REQUIRE(K >= 2 && K <= KMAX, SSIP_ERR_ARG, "ssip_kmeans_assign: K = %d outside 2..64", K);
+  SSIP_REQUIRE(centres && labels && mind2 && workspace, SSIP_ERR_ARG, "ssip_kmeans_assign: null pointer");
+  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
+               "ssip_kmeans_assign: workspace must be 16-byte aligned");
+  SSIP_REQUIRE(workspace_bytes >= kmeans_ws_bytes(N, d, K), SSIP_ERR_WORKSPACE,
+               "ssip_kmeans_assign: workspace of %ld bytes, need %ld", (long)workspace_bytes,
+               kmeans_ws_bytes(N, d, K));
+  const long G = kmeans_groups(N);
+  SSIP_REQUIRE(G <= 0x7fffffffL, SSIP_ERR_ARG, "ssip_kmeans_assign: N = %ld too large", (long)N);
+  SSIP_KLAUNCH(kmeans_assign_kernel, dim3((unsigned)G), dim3(NT), 0, (hipStream_t)stream, (long)N, d, K, X, centres,
+               prev_labels, labels, mind2, kmeans_ws(workspace, N, d, K));
+  return ssip::check_launch("ssip_kmeans_assign");
+}
+
+int ssip_kmeans_update(int64_t N, int d, int K, const void* workspace, int64_t workspace_bytes, const float* centres,
+                       float* new_centres, int32_t* counts, double* scalars, void* stream) {
+  SSIP_REQUIRE(N >= 1 && d >= 1 && d <= 512 && K >= 2 && K <= KMAX, SSIP_ERR_ARG,
+               "ssip_kmeans_update: need N >= 1, 1 <= d <= 512, 2 <= K <= 64 (N=%ld d=%d K=%d)", (long)N, d, K);
+  SSIP_REQUIRE(workspace && centres && new_centres && counts && scalars, SSIP_ERR_ARG,
+               "ssip_kmeans_update: null pointer");
+  SSIP_REQUIRE(workspace_bytes >= kmeans_ws_bytes(N, d, K), SSIP_ERR_WORKSPACE,
+               "ssip_kmeans_update: workspace of %ld bytes, need %ld", (long)workspace_bytes,
+               kmeans_ws_bytes(N, d, K));
+  SSIP_KLAUNCH(kmeans_update_kernel, dim3(1), dim3(UPD_NT), 0, (hipStream_t)stream, kmeans_groups(N), d, K,
+               kmeans_ws(const_cast<void*>(workspace), N, d, K), centres, new_centres, counts, scalars);
+  return ssip::check_launch("ssip_kmeans_update");
+}
+
+int ssip_pairwise_eps(int N, int d, const float* X, float eps, int32_t* degree, uint32_t* bitmap, void* stream) {
+  if (int rc = check_points("ssip_pairwise_eps", N, d, X)) return rc;
+  SSIP_REQUIRE(N <= 65536, SSIP_ERR_ARG,
+               "ssip_pairwise_eps: N = %d above 65536 (the adjacency bitmap would exceed 512 MB)", N);
+  SSIP_REQUIRE(eps >= 0.f, SSIP_ERR_ARG, "ssip_pairwise_eps: eps = %g must be >= 0", (double)eps);
+  SSIP_REQUIRE(degree && bitmap, SSIP_ERR_ARG, "ssip_pairwise_eps: null pointer");
+  SSIP_KLAUNCH(pairwise_a_kernel<0>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps, 1,
+               degree, bitmap, (float*)nullptr);
+  return ssip::check_launch("ssip_pairwise_eps");
+}
+
+int ssip_pairwise_kth(int N, int d, int k, const float* X, float* kth, void* stream) {
+  if (int rc = check_points("ssip_pairwise_kth", N, d, X)) return rc;
+  SSIP_REQUIRE(k >= 1 && k <= 64, SSIP_ERR_ARG, "ssip_pairwise_kth: k = %d outside 1..64", k);
+  SSIP_REQUIRE(k <= N, SSIP_ERR_ARG, "ssip_pairwise_kth: k = %d neighbours asked of N = %d points", k, N);
+  SSIP_REQUIRE(kth != nullptr, SSIP_ERR_ARG, "ssip_pairwise_kth: null pointer");
+  SSIP_KLAUNCH(pairwise_a_kernel<1>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, 0.f, k,
+               (int*)nullptr, (uint32_t*)nullptr, kth);
+  return ssip::check_launch("ssip_pairwise_kth");
+}
+
+int ssip_pairwise_cluster_sums(int N, int d, int K, const float* X, const int32_t* labels, const int32_t* order,
+                               float* sums, void* stream) {
+  if (int rc = check_points("ssip_pairwise_cluster_sums", N, d, X)) return rc;
+  SSIP_REQUIRE(K >= 1 && K <= 256, SSIP_ERR_ARG, "ssip_pairwise_cluster_sums: K = %d outside 1..256", K);
+  SSIP_REQUIRE(labels && order && sums, SSIP_ERR_ARG, "ssip_pairwise_cluster_sums: null pointer");
+  // a cluster without members keeps a zero column
+  if (hipMemsetAsync(sums, 0, (size_t)N * K * sizeof(float), (hipStream_t)stream) != hipSuccess) {
+    ssip::set_error("ssip_pairwise_cluster_sums: hipMemsetAsync failed");
+    return SSIP_ERR_LAUNCH;
+  }
+  SSIP_KLAUNCH(cluster_sums_kernel, dim3((N + RB - 1) / RB), dim3(NT), 0, (hipStream_t)stream, N, d, K, X, labels,
+               order, sums);
+  return ssip::check_launch("ssip_pairwise_cluster_sums");
+}
+
+}  // extern "C"

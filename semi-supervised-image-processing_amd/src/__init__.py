@@ -3,6 +3,8 @@
     python -m src.semi_supervised_training --strong-data-dir ... --weak-data-dir ...
     python -m src.supervised_training --strong-data-dir ...
     python -m src.feature_extraction --data-dir ...
+    python -m src.standardize_features
+    python -m src.clustering --features-npz outputs/features/standardized_features.npz
 
 As in the reference (src/semi_supervised_training.py:19-20), the training
 CLIs import `training.*`, so this directory is put on sys.path; the parent

@@ -29,7 +29,7 @@ def abi_version_expected() -> int:
     return int(m.group(1)) if m else ABI_VERSION
 
 
-ABI_VERSION = 14  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
+ABI_VERSION = 15  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
 
 F32 = 0
 BF16 = 1
@@ -137,6 +137,13 @@ _SIGS = {
     "ssip_weight_prep": (_c_int, [_c_int] * 7 + [_vp, _vp, _vp, _vp]),
     "ssip_weight_prep_batch": (_c_int, [_c_int, _c_int, ctypes.POINTER(WPrep), _vp]),
     "ssip_counters_add": (_c_int, [_c_int, _vp, _c_i64, _vp]),
+    # embedding analytics (ssip/analytics.py)
+    "ssip_kmeans_workspace_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
+    "ssip_kmeans_assign": (_c_int, [_c_i64, _c_int, _c_int] + [_vp] * 6 + [_c_i64, _vp]),
+    "ssip_kmeans_update": (_c_int, [_c_i64, _c_int, _c_int, _vp, _c_i64] + [_vp] * 5),
+    "ssip_pairwise_eps": (_c_int, [_c_int, _c_int, _vp, _c_f, _vp, _vp, _vp]),
+    "ssip_pairwise_kth": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ssip_pairwise_cluster_sums": (_c_int, [_c_int, _c_int, _c_int] + [_vp] * 5),
     # launch plans (ssip/plan.py)
     "ssip_plan_create": (_vp, []),
     "ssip_plan_destroy": (None, [_vp]),

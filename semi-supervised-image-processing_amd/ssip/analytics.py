@@ -1,0 +1,430 @@
+"""Embedding analytics: K-Means, DBSCAN, silhouette and the k-distance curve
+over the PCA cluster space (reference src/clustering.py:330-438).
+
+The O(N*K*d) and O(N^2*d) distance work runs in the kernels of
+csrc/analytics.hip; what stays on the host is the control flow around them:
+
+* ``kmeans_fit`` replays ``sklearn.cluster.KMeans(n_init=..., random_state=
+  seed)``: centre X by its column mean (in X's dtype), ``tol = mean(var(Xc)) *
+  1e-4``, one shared ``RandomState`` over the inits, k-means++ seeding through
+  the public ``sklearn.cluster.kmeans_plusplus`` on the host, then a plain
+  Lloyd loop on the backend (stop on unchanged labels or on a squared centre
+  shift <= tol, at most 300 iterations, one final assignment), keeping the
+  lowest-inertia init.
+* ``dbscan`` labels by sklearn's order-free rule: cluster ids are the
+  connected components of the core-point graph numbered by their lowest core
+  index, a border point takes the smallest id among its core neighbours,
+  everything else is -1.
+* ``silhouette`` finishes a, b and s in fp64 from per-cluster distance sums.
+
+The Lloyd driver and the DBSCAN labeller work on a small backend object
+(``assign`` / ``update`` / ``eps_graph`` / ...).  ``DeviceBackend`` launches
+the HIP kernels; ``NumpyBackend`` is the opt-in host path (``--device cpu`` of
+``src.clustering``, like ssip/host.py) and lets the host logic be tested
+without a GPU.  Nothing here falls back from one to the other.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+
+MAX_ITER = 300
+TOL = 1e-4
+KTH_MAX = 64
+EPS_MAX_N = 65536
+SILHOUETTE_MAX_K = 256
+
+
+# ---------------------------------------------------------------------------
+# host pieces shared by both backends
+# ---------------------------------------------------------------------------
+def pack_adjacency(adj: np.ndarray) -> np.ndarray:
+    """bool [R][N] -> uint32 [R][ceil(N/32)], bit (j % 32) of word j / 32 = adj[i][j]."""
+    adj = np.asarray(adj, dtype=bool)
+    rows, n = adj.shape
+    words = (n + 31) // 32
+    padded = np.zeros((rows, words * 32), dtype=bool)
+    padded[:, :n] = adj
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4").reshape(rows, words)
+
+
+def _bits_to_indices(words: np.ndarray, n: int) -> np.ndarray:
+    return np.flatnonzero(np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n])
+
+
+def dbscan_labels_from_graph(degree: np.ndarray, bitmap: np.ndarray, min_samples: int) -> np.ndarray:
+    """sklearn.cluster.DBSCAN's labels from the eps graph (degree counts self).
+
+    ``bitmap`` is the packed adjacency (``pack_adjacency``) or a dense bool
+    [N][N] matrix.  Components are grown breadth-first over the bitmap rows of
+    core points, from seeds in increasing index, so ids come out numbered by
+    their lowest core index and a border point keeps the first (= smallest)
+    id that reaches it.
+    """
+    bitmap = np.asarray(bitmap)
+    if bitmap.dtype == bool:
+        bitmap = pack_adjacency(bitmap)
+    degree = np.asarray(degree)
+    n = degree.shape[0]
+    core = degree >= int(min_samples)
+    labels = np.full(n, -1, dtype=np.int64)
+    cid = 0
+    for seed in np.flatnonzero(core):
+        if labels[seed] != -1:
+            continue
+        visited = np.zeros(bitmap.shape[1], dtype=np.uint32)
+        visited[seed >> 5] = np.uint32(1) << np.uint32(seed & 31)
+        frontier = np.array([seed])
+        while frontier.size:
+            reach = np.bitwise_or.reduce(bitmap[frontier], axis=0)
+            new = reach & ~visited
+            visited |= new
+            idx = _bits_to_indices(new, n)
+            frontier = idx[core[idx]]
+        members = _bits_to_indices(visited, n)
+        take = members[core[members] | (labels[members] == -1)]
+        labels[take] = cid
+        cid += 1
+    return labels
+
+
+def _relocate_empty(X: np.ndarray, labels: np.ndarray, mind2: np.ndarray, old: np.ndarray) -> np.ndarray:
+    """New centres when some cluster attracted no point, as sklearn's dense
+    relocation does: each empty centre moves to one of the points farthest from
+    its own centre, and that point leaves its donor cluster's sum."""
+    k = old.shape[0]
+    counts = np.bincount(labels, minlength=k).astype(np.float64)
+    sums = np.zeros((k, X.shape[1]), dtype=np.float64)
+    for c in np.flatnonzero(counts):
+        sums[c] = X[labels == c].sum(axis=0, dtype=np.float64)
+    empty = np.flatnonzero(counts == 0)
+    n_empty = empty.size
+    far = np.argpartition(mind2, -n_empty)[: -n_empty - 1: -1]
+    for new_id, far_idx in zip(empty, far):
+        donor = labels[far_idx]
+        sums[donor] -= X[far_idx]
+        sums[new_id] = X[far_idx]
+        counts[new_id] = 1
+        counts[donor] -= 1
+    new = old.astype(np.float64).copy()
+    nz = counts > 0
+    new[nz] = sums[nz] / counts[nz, None]
+    return new.astype(old.dtype)
+
+
+def _same_clustering(a: np.ndarray, b: np.ndarray, k: int) -> bool:
+    """True when the labels of a map one-to-one onto those of b (sklearn's
+    check before it lets a later init replace the best one)."""
+    return np.unique(a.astype(np.int64) * k + b).size == np.unique(a).size
+
+
+# ---------------------------------------------------------------------------
+# backends
+# ---------------------------------------------------------------------------
+class NumpyBackend:
+    """Host backend: fp64 direct-difference distances (scipy cdist), the same
+    method surface and bitmap format as the device backend."""
+
+    name = "cpu"
+
+    def __init__(self, X: np.ndarray):
+        X = np.asarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self.X = np.ascontiguousarray(X)
+        self.n, self.d = self.X.shape
+
+    def _row_chunks(self, cols: int):
+        step = max(1, (1 << 22) // max(cols, 1))
+        for s in range(0, self.n, step):
+            yield s, min(self.n, s + step)
+
+    # -- K-Means --------------------------------------------------------------
+    def begin(self, centres: np.ndarray) -> None:
+        self.C = np.array(centres, dtype=self.X.dtype)
+        self.Cn = self.C.copy()
+        self._labels = np.full(self.n, -1, dtype=np.int32)
+        self._prev = self._labels.copy()
+        self._mind2 = np.zeros(self.n, dtype=np.float64)
+
+    def assign(self) -> None:
+        from scipy.spatial.distance import cdist
+
+        self._prev, self._labels = self._labels, self._prev
+        for s, e in self._row_chunks(self.C.shape[0]):
+            d2 = cdist(self.X[s:e], self.C, "sqeuclidean")
+            lab = np.argmin(d2, axis=1)
+            self._labels[s:e] = lab
+            self._mind2[s:e] = d2[np.arange(e - s), lab]
+
+    def update(self) -> Tuple[float, float, int, int]:
+        k = self.C.shape[0]
+        counts = np.bincount(self._labels, minlength=k)
+        new = self.C.astype(np.float64).copy()
+        for c in np.flatnonzero(counts):
+            new[c] = self.X[self._labels == c].sum(axis=0, dtype=np.float64) / counts[c]
+        self.Cn = new.astype(self.X.dtype)
+        self.counts = counts
+        shift2 = float(((self.Cn.astype(np.float64) - self.C) ** 2).sum())
+        changed = int(np.count_nonzero(self._labels != self._prev))
+        return shift2, float(self._mind2.sum()), changed, int(np.count_nonzero(counts == 0))
+
+    def relocate(self) -> float:
+        self.Cn = _relocate_empty(self.X, self._labels, self._mind2, self.C)
+        return float(((self.Cn.astype(np.float64) - self.C) ** 2).sum())
+
+    def swap(self) -> None:
+        self.C, self.Cn = self.Cn, self.C
+
+    def labels(self) -> np.ndarray:
+        return self._labels.copy()
+
+    def centres(self) -> np.ndarray:
+        return self.C.copy()
+
+    # -- pairwise ---------------------------------------------------------------
+    def eps_graph(self, eps: float) -> Tuple[np.ndarray, np.ndarray]:
+        from scipy.spatial.distance import cdist
+
+        words = (self.n + 31) // 32
+        degree = np.zeros(self.n, dtype=np.int32)
+        bitmap = np.zeros((self.n, words), dtype=np.uint32)
+        e2 = float(eps) * float(eps)
+        for s, e in self._row_chunks(self.n):
+            adj = cdist(self.X[s:e], self.X, "sqeuclidean") <= e2
+            degree[s:e] = adj.sum(axis=1)
+            bitmap[s:e] = pack_adjacency(adj)
+        return degree, bitmap
+
+    def kth(self, k: int) -> np.ndarray:
+        from scipy.spatial.distance import cdist
+
+        out = np.zeros(self.n, dtype=np.float64)
+        for s, e in self._row_chunks(self.n):
+            d2 = cdist(self.X[s:e], self.X, "sqeuclidean")
+            out[s:e] = np.sqrt(np.partition(d2, k - 1, axis=1)[:, k - 1])
+        return out
+
+    def cluster_sums(self, enc: np.ndarray, order: np.ndarray, k: int) -> np.ndarray:
+        from scipy.spatial.distance import cdist
+
+        sums = np.zeros((self.n, k), dtype=np.float64)
+        starts = np.searchsorted(enc[order], np.arange(k))
+        for s, e in self._row_chunks(self.n):
+            dist = cdist(self.X[s:e], self.X[order], "euclidean")
+            sums[s:e] = np.add.reduceat(dist, starts, axis=1)
+        return sums
+
+
+class DeviceBackend:
+    """libssip_hip.so backend (csrc/analytics.hip).  torch only owns the
+    buffers and the stream; every distance is computed by the HIP kernels."""
+
+    name = "cuda"
+
+    def __init__(self, X: np.ndarray):
+        import torch
+
+        from . import _lib, ops
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("ssip.analytics: the device backend needs the HIP device (use device='cpu' for the "
+                               "host path)")
+        self._torch, self._lib, self._ops = torch, _lib, ops
+        self.Xh = np.ascontiguousarray(X, dtype=np.float32)
+        self.n, self.d = self.Xh.shape
+        if not 1 <= self.d <= 512:
+            raise ValueError(f"ssip.analytics: feature dimension {self.d} outside 1..512")
+        self.dev = torch.device("cuda")
+        self.X = torch.from_numpy(self.Xh).to(self.dev)
+
+    def _call(self, name, *args):
+        return self._lib.call(name, *args, self._ops.stream_ptr())
+
+    def _p(self, t):
+        return self._lib.ptr(t)
+
+    # -- K-Means --------------------------------------------------------------
+    def begin(self, centres: np.ndarray) -> None:
+        t = self._torch
+        k = centres.shape[0]
+        self.k = k
+        self.C = t.from_numpy(np.ascontiguousarray(centres, dtype=np.float32)).to(self.dev)
+        self.Cn = t.empty_like(self.C)
+        self._labels = t.full((self.n,), -1, dtype=t.int32, device=self.dev)
+        self._prev = t.full((self.n,), -1, dtype=t.int32, device=self.dev)
+        self._mind2 = t.empty(self.n, dtype=t.float32, device=self.dev)
+        self._ws_bytes = int(self._lib.call("ssip_kmeans_workspace_bytes", self.n, self.d, k))
+        if self._ws_bytes < 0:
+            self._lib.check(self._ws_bytes, "ssip_kmeans_workspace_bytes")
+        self._ws = t.empty(self._ws_bytes, dtype=t.uint8, device=self.dev)
+        self._counts = t.empty(k, dtype=t.int32, device=self.dev)
+        self._scalars = t.empty(4, dtype=t.float64, device=self.dev)
+
+    def assign(self) -> None:
+        self._prev, self._labels = self._labels, self._prev
+        self._call("ssip_kmeans_assign", self.n, self.d, self.k, self._p(self.X), self._p(self.C),
+                   self._p(self._prev), self._p(self._labels), self._p(self._mind2), self._p(self._ws),
+                   self._ws_bytes)
+
+    def update(self) -> Tuple[float, float, int, int]:
+        self._call("ssip_kmeans_update", self.n, self.d, self.k, self._p(self._ws), self._ws_bytes, self._p(self.C),
+                   self._p(self.Cn), self._p(self._counts), self._p(self._scalars))
+        s = self._scalars.cpu().numpy()  # the one read-back of an iteration
+        return float(s[0]), float(s[1]), int(s[2]), int(s[3])
+
+    def relocate(self) -> float:
+        old = self.C.cpu().numpy()
+        new = _relocate_empty(self.Xh, self._labels.cpu().numpy(), self._mind2.cpu().numpy(), old)
+        self.Cn.copy_(self._torch.from_numpy(new))
+        return float(((new.astype(np.float64) - old) ** 2).sum())
+
+    def swap(self) -> None:
+        self.C, self.Cn = self.Cn, self.C
+
+    def labels(self) -> np.ndarray:
+        return self._labels.cpu().numpy()
+
+    def centres(self) -> np.ndarray:
+        return self.C.cpu().numpy()
+
+    # -- pairwise ---------------------------------------------------------------
+    def eps_graph(self, eps: float) -> Tuple[np.ndarray, np.ndarray]:
+        t = self._torch
+        if self.n > EPS_MAX_N:
+            raise ValueError(f"ssip.analytics: the eps graph supports N <= {EPS_MAX_N} (got {self.n})")
+        words = (self.n + 31) // 32
+        degree = t.empty(self.n, dtype=t.int32, device=self.dev)
+        bitmap = t.empty((self.n, words), dtype=t.int32, device=self.dev)
+        self._call("ssip_pairwise_eps", self.n, self.d, self._p(self.X), float(eps), self._p(degree),
+                   self._p(bitmap))
+        return degree.cpu().numpy(), bitmap.cpu().numpy().view(np.uint32)
+
+    def kth(self, k: int) -> np.ndarray:
+        t = self._torch
+        out = t.empty(self.n, dtype=t.float32, device=self.dev)
+        self._call("ssip_pairwise_kth", self.n, self.d, int(k), self._p(self.X), self._p(out))
+        return out.cpu().numpy().astype(np.float64)
+
+    def cluster_sums(self, enc: np.ndarray, order: np.ndarray, k: int) -> np.ndarray:
+        t = self._torch
+        if k > SILHOUETTE_MAX_K:
+            raise ValueError(f"ssip.analytics: silhouette supports at most {SILHOUETTE_MAX_K} clusters on the device "
+                             f"(got {k})")
+        lab = t.from_numpy(np.ascontiguousarray(enc, dtype=np.int32)).to(self.dev)
+        ordr = t.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(self.dev)
+        sums = t.empty((self.n, k), dtype=t.float32, device=self.dev)
+        self._call("ssip_pairwise_cluster_sums", self.n, self.d, int(k), self._p(self.X), self._p(lab),
+                   self._p(ordr), self._p(sums))
+        return sums.cpu().numpy().astype(np.float64)
+
+
+def make_backend(X: np.ndarray, device: str = "cuda"):
+    """'cuda' -> the HIP kernels, 'cpu' -> the numpy host path (explicit opt-in)."""
+    if device == "cuda":
+        return DeviceBackend(X)
+    if device == "cpu":
+        return NumpyBackend(X)
+    raise ValueError(f"ssip.analytics: unknown device {device!r} (cuda or cpu)")
+
+
+# ---------------------------------------------------------------------------
+# public functions
+# ---------------------------------------------------------------------------
+def lloyd(backend, centres: np.ndarray, tol: float, max_iter: int = MAX_ITER):
+    """One K-Means run from the given centres: (labels, inertia, centres, iterations)."""
+    backend.begin(centres)
+    strict = False
+    inertia = float("nan")
+    it = 0
+    for it in range(1, max_iter + 1):
+        backend.assign()
+        shift2, inertia, changed, n_empty = backend.update()
+        if n_empty:
+            shift2 = backend.relocate()
+        backend.swap()
+        if changed == 0:
+            # same labels -> the same means: the inertia above is already that
+            # of the final centres
+            strict = True
+            break
+        if shift2 <= tol:
+            break
+    if not strict:
+        backend.assign()
+        inertia = backend.update()[1]  # labels and inertia against the final centres; no swap
+    return backend.labels(), inertia, backend.centres(), it
+
+
+def kmeans_fit(X: np.ndarray, k: int, n_init: int = 10, seed: int = 42, device: str = "cuda",
+               max_iter: int = MAX_ITER, tol: float = TOL):
+    """(labels int32 [N], inertia, centres [k][d]) of KMeans(n_clusters=k, n_init, random_state=seed)."""
+    from sklearn.cluster import kmeans_plusplus
+
+    X = np.asarray(X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    if device == "cuda":
+        X = X.astype(np.float32, copy=False)
+    if not 2 <= int(k) <= 64:
+        raise ValueError(f"ssip.analytics: k = {k} outside 2..64")
+    if X.shape[0] < k:
+        raise ValueError(f"ssip.analytics: n_samples={X.shape[0]} should be >= n_clusters={k}")
+    mean = X.mean(axis=0)
+    Xc = X - mean
+    tol_abs = float(np.mean(np.var(Xc, axis=0)) * tol)
+    rs = np.random.RandomState(seed)
+    backend = make_backend(Xc, device)
+    best = None
+    for _ in range(int(n_init)):
+        init, _ = kmeans_plusplus(Xc, int(k), random_state=rs)
+        labels, inertia, centres, _ = lloyd(backend, init, tol_abs, max_iter)
+        if best is None or (inertia < best[1] and not _same_clustering(labels, best[0], int(k))):
+            best = (labels, inertia, centres)
+    labels, inertia, centres = best
+    return labels.astype(np.int32), float(inertia), centres + mean
+
+
+def dbscan(X: np.ndarray, eps: float, min_samples: int, device: str = "cuda", backend=None) -> np.ndarray:
+    """Labels of sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(X)."""
+    backend = backend if backend is not None else make_backend(X, device)
+    degree, bitmap = backend.eps_graph(float(eps))
+    return dbscan_labels_from_graph(degree, bitmap, int(min_samples))
+
+
+def silhouette(X: np.ndarray, labels: np.ndarray, device: str = "cuda", backend=None) -> float:
+    """sklearn.metrics.silhouette_score(X, labels) (a -1 noise label is a cluster
+    of its own); NaN for fewer than 2 distinct labels or as many labels as points."""
+    labels = np.asarray(labels)
+    n = labels.shape[0]
+    uniq, enc = np.unique(labels, return_inverse=True)
+    k = uniq.size
+    if k < 2 or k >= n:
+        return float("nan")
+    backend = backend if backend is not None else make_backend(X, device)
+    enc = enc.astype(np.int32)
+    order = np.argsort(enc, kind="stable").astype(np.int32)
+    sums = np.asarray(backend.cluster_sums(enc, order, k), dtype=np.float64)
+    counts = np.bincount(enc, minlength=k).astype(np.float64)
+    rows = np.arange(n)
+    own = counts[enc]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = sums[rows, enc] / (own - 1.0)
+        other = sums / counts[None, :]
+        other[rows, enc] = np.inf
+        b = other.min(axis=1)
+        s = (b - a) / np.maximum(a, b)
+    s[own == 1] = 0.0
+    return float(np.mean(np.nan_to_num(s)))
+
+
+def kth_neighbor_distance(X: np.ndarray, k: int, device: str = "cuda", backend=None) -> np.ndarray:
+    """NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1] (self at distance 0)."""
+    n = np.asarray(X).shape[0]
+    if not 1 <= int(k) <= KTH_MAX:
+        raise ValueError(f"ssip.analytics: k = {k} outside 1..{KTH_MAX}")
+    if int(k) > n:
+        raise ValueError(f"ssip.analytics: Expected n_neighbors <= n_samples, but n_neighbors = {k}, n_samples = {n}")
+    backend = backend if backend is not None else make_backend(X, device)
+    return backend.kth(int(k))
