@@ -25,6 +25,8 @@
  *     -> ssip_semi_loss
  *   KMeans / DBSCAN / silhouette_score / kneighbors   src/clustering.py:330-438
  *     -> ssip_kmeans_assign / _update, ssip_pairwise_eps / _kth / _cluster_sums
+ *   TSNE(...).fit_transform                  src/clustering.py:251-276
+ *     -> ssip_tsne_cond_p / _joint_p / _grad / _update (the exact objective)
  *
  * Conventions
  *   - Every pointer is a device pointer unless documented otherwise; the
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SSIP_ABI_VERSION 15
+#define SSIP_ABI_VERSION 16
 
 enum ssip_dtype { SSIP_F32 = 0, SSIP_BF16 = 1 };
 enum ssip_status { SSIP_OK = 0, SSIP_ERR_ARG = -1, SSIP_ERR_LAUNCH = -2, SSIP_ERR_WORKSPACE = -3 };
@@ -431,6 +433,50 @@ int ssip_pairwise_kth(int N, int d, int k, const float* X, float* kth, void* str
  * of labels (host).  Columns are visited in `order`. */
 int ssip_pairwise_cluster_sums(int N, int d, int K, const float* X, const int32_t* labels, const int32_t* order,
                                float* sums, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Exact t-SNE (reference src/clustering.py:251-276 run_tsne, which calls
+ * sklearn.manifold.TSNE; the objective and the step are those of sklearn's
+ * _t_sne.py with method="exact").  2 <= N <= 32768: P is fp32 [N][N] (4 GB at
+ * the cap), the embedding Y is fp32 [N][2].  No atomics, every reduction in
+ * a fixed order (bit-reproducible).  One workspace (16-byte aligned) serves
+ * joint_p, grad and update.
+ * ---------------------------------------------------------------------- */
+/* bytes of that workspace; an argument error for N outside 2..32768 */
+int64_t ssip_tsne_workspace_bytes(int64_t N);
+/* P[i][j] = p(j|i) of sklearn's _binary_search_perplexity over the squared
+ * distances of X (fp32 [N][d], 1 <= d <= 512; direct difference, feature
+ * order, as the analytics section): beta from 1, doubled or halved until
+ * bracketed, then bisected, at most 100 steps, until |H - log(perplexity)| <=
+ * 1e-5; a zero row sum counts as 1e-8.  exp and the entropy sums are fp64, so
+ * a row whose every exp(-d2) underflows halves its way down as sklearn does.
+ * P[i][i] = 0.  beta[N] (fp64) = the precision each row of P was built with. */
+int ssip_tsne_cond_p(int N, int d, const float* X, float perplexity, float* P, double* beta, void* stream);
+/* In place: P[i][j] = (p(j|i) + p(i|j)) / sum of all entries of the
+ * symmetrised matrix (fixed order, the last level in fp64).  Symmetric bit
+ * for bit. */
+int ssip_tsne_joint_p(int N, float* P, void* workspace, int64_t workspace_bytes, void* stream);
+/* One pass over all pairs with w_ij = 1 / (1 + |y_i - y_j|^2): per row and
+ * column split, partials of attr_i = sum_j P_ij w_ij (y_i - y_j), rep_i =
+ * sum_j w_ij^2 (y_i - y_j), z_i = sum_{j != i} w_ij and, when compute_error is
+ * non-zero, of the row's share of sum P log P - sum P log w.  They stay in the
+ * workspace for ssip_tsne_update. */
+int ssip_tsne_grad(int N, const float* P, const float* Y, int compute_error, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+/* Reduces the partials of the preceding ssip_tsne_grad in split order (Z =
+ * sum z_i and the error sum in fp64), grad_i = 4 (exaggeration attr_i - rep_i
+ * / Z), then sklearn's step on Y, update and gains (all fp32 [N][2]): gains +=
+ * 0.2 where update * grad < 0, *= 0.8 elsewhere, floor 0.01; update =
+ * momentum * update - learning_rate * gains * grad; Y += update, each
+ * operation rounded to fp32.  scalars (4 fp64): {Z, KL divergence of the
+ * unexaggerated P at the Y the gradient was taken at (meaningful when that
+ * gradient ran with compute_error), |grad|, |gains * grad| (the norm sklearn
+ * stops on)}.  Afterwards the workspace holds, behind a head of (4 *
+ * ceil(N / 256) + 1) * 8 bytes rounded up to 16, the reduced row sums fp32
+ * [6][N] (attr x, attr y, rep x, rep y, z, error share) and then grad fp32
+ * [N][2]. */
+int ssip_tsne_update(int N, void* workspace, int64_t workspace_bytes, float* Y, float* update, float* gains,
+                     float exaggeration, float momentum, float learning_rate, double* scalars, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the stream-ordered entry points

@@ -17,11 +17,15 @@ What runs where:
   * K-Means (:340-373), DBSCAN (:376-428), the silhouette score (:330-337) and
     the k-distance curve (:430-438, :541-563) go through ssip.analytics.
     ``--device cuda`` (and ``auto``) uses the HIP kernels; ``--device cpu`` is
-    an explicit host path on the same driver with the numpy backend.  One
-    extension flag: ``--device``.
-  * Standardisation checks, PCA (sklearn, svd_solver="full": the reference's
-    cluster space bit for bit) and t-SNE (sklearn) stay on the host: O(N*D^2)
-    at most, against O(N^2*d) per DBSCAN / silhouette configuration.
+    an explicit host path on the same driver with the numpy backend.  Two
+    extension flags: ``--device`` and ``--tsne-method``.
+  * Standardisation checks and PCA (sklearn, svd_solver="full": the reference's
+    cluster space bit for bit) stay on the host: O(N*D^2) at most, against
+    O(N^2*d) per DBSCAN / silhouette configuration.
+  * t-SNE is the reference's sklearn Barnes-Hut call by default.
+    ``--tsne-method exact`` runs the exact objective under sklearn's schedule
+    through ssip.analytics.tsne_fit (csrc/tsne.hip) on the resolved --device,
+    with the same artefact names, npz keys and params.
   * UMAP runs through ``umap`` when that package imports; when it does not, one
     warning is logged and the UMAP grid is empty, for which the assignments
     table names pca_2d as umap_id (the reference's behaviour for an empty grid,
@@ -49,6 +53,7 @@ METRIC_COLUMNS = ("method", "space", "params_json", "ARI", "NMI", "silhouette", 
 ASSIGNMENT_COLUMNS = ("path", "cluster_kmeans", "cluster_dbscan", "pca_dim", "tsne_id", "umap_id", "is_labeled",
                       "true_label")
 SCOPES = ("all", "labeled", "unlabeled")
+TSNE_METHODS = ("barnes_hut", "exact")
 
 
 @dataclass(frozen=True)
@@ -166,14 +171,27 @@ def run_pca(features: np.ndarray, variance_target: float, tsne_dim: int, seed: i
     )
 
 
-def run_tsne(base: EmbeddingResult, perplexities: Sequence[float], seed: int) -> List[EmbeddingResult]:
+def run_tsne(base: EmbeddingResult, perplexities: Sequence[float], seed: int, method: str = "barnes_hut",
+             device: str = "cuda") -> List[EmbeddingResult]:
+    """barnes_hut: the reference's sklearn call.  exact: ssip.analytics.tsne_fit
+    (csrc/tsne.hip on ``device`` cuda, the numpy path on cpu); above its N cap
+    one warning is logged and the sklearn call runs instead."""
     from sklearn.manifold import TSNE
 
+    if method not in TSNE_METHODS:
+        raise ValueError("t-SNE method must be one of: " + ", ".join(TSNE_METHODS))
+    if method == "exact" and base.data.shape[0] > analytics.TSNE_MAX_N:
+        logging.warning("exact t-SNE supports N <= %s (got %s): using the sklearn Barnes-Hut call",
+                        analytics.TSNE_MAX_N, base.data.shape[0])
+        method = "barnes_hut"
     out = []
     for perp in perplexities:
-        logging.info("Running t-SNE (perplexity=%s)", perp)
-        emb = TSNE(n_components=2, perplexity=float(perp), init="pca", random_state=seed, learning_rate="auto",
-                   max_iter=1000, metric="euclidean").fit_transform(base.data)
+        logging.info("Running t-SNE (perplexity=%s, method=%s)", perp, method)
+        if method == "exact":
+            emb, _, _ = analytics.tsne_fit(base.data, float(perp), seed=seed, max_iter=1000, device=device)
+        else:
+            emb = TSNE(n_components=2, perplexity=float(perp), init="pca", random_state=seed, learning_rate="auto",
+                       max_iter=1000, metric="euclidean").fit_transform(base.data)
         out.append(EmbeddingResult(f"tsne_perp{int(perp)}", np.asarray(emb), {"perplexity": float(perp), "seed": seed}))
     return out
 
@@ -430,6 +448,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--device", type=str, default="auto", choices=["auto", "cuda", "cpu"],
                    help="Where K-Means, DBSCAN, silhouette and the k-distance curve run: auto/cuda = the HIP kernels, "
                         "cpu = the numpy host path of the same driver.")
+    p.add_argument("--tsne-method", type=str, default="barnes_hut", choices=list(TSNE_METHODS),
+                   help="barnes_hut = sklearn's TSNE on the host (the reference's call); exact = the exact objective "
+                        "through ssip.analytics.tsne_fit on --device.")
     return p.parse_args(argv)
 
 
@@ -446,7 +467,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
 
     pca = run_pca(bundle.features, args.variance_target, args.tsne_dim, args.seed)
     emb_dir = args.output_root / "features" / "dimensionality_reduction"
-    tsne = run_tsne(pca.pca_tsne_init, args.tsne_perplexities, args.seed)
+    tsne = run_tsne(pca.pca_tsne_init, args.tsne_perplexities, args.seed, args.tsne_method, device)
     umaps = run_umap(pca.pca_tsne_init, args.umap_neighbors, args.umap_min_dist, args.seed)
     for emb in [pca.cluster_space, pca.pca_2d, pca.pca_tsne_init, *tsne, *umaps]:
         save_embedding_npz(emb_dir, emb)

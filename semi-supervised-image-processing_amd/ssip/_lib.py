@@ -29,7 +29,7 @@ def abi_version_expected() -> int:
     return int(m.group(1)) if m else ABI_VERSION
 
 
-ABI_VERSION = 15  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
+ABI_VERSION = 16  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
 
 F32 = 0
 BF16 = 1
@@ -144,6 +144,12 @@ _SIGS = {
     "ssip_pairwise_eps": (_c_int, [_c_int, _c_int, _vp, _c_f, _vp, _vp, _vp]),
     "ssip_pairwise_kth": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "ssip_pairwise_cluster_sums": (_c_int, [_c_int, _c_int, _c_int] + [_vp] * 5),
+    # exact t-SNE (ssip/analytics.py)
+    "ssip_tsne_workspace_bytes": (_c_i64, [_c_i64]),
+    "ssip_tsne_cond_p": (_c_int, [_c_int, _c_int, _vp, _c_f, _vp, _vp, _vp]),
+    "ssip_tsne_joint_p": (_c_int, [_c_int, _vp, _vp, _c_i64, _vp]),
+    "ssip_tsne_grad": (_c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_i64, _vp]),
+    "ssip_tsne_update": (_c_int, [_c_int, _vp, _c_i64, _vp, _vp, _vp, _c_f, _c_f, _c_f, _vp, _vp]),
     # launch plans (ssip/plan.py)
     "ssip_plan_create": (_vp, []),
     "ssip_plan_destroy": (None, [_vp]),

@@ -16,6 +16,11 @@ csrc/analytics.hip; what stays on the host is the control flow around them:
   index, a border point takes the smallest id among its core neighbours,
   everything else is -1.
 * ``silhouette`` finishes a, b and s in fp64 from per-cluster distance sums.
+* ``tsne_fit`` is sklearn's exact t-SNE (``TSNE(method="exact", init="pca",
+  learning_rate="auto")``): the joint probabilities once (csrc/tsne.hip), then
+  sklearn's two-phase schedule of gradient and momentum / gains steps with one
+  read-back of four scalars on every 50th iteration and nothing else crossing
+  the bus.
 
 The Lloyd driver and the DBSCAN labeller work on a small backend object
 (``assign`` / ``update`` / ``eps_graph`` / ...).  ``DeviceBackend`` launches
@@ -34,6 +39,11 @@ TOL = 1e-4
 KTH_MAX = 64
 EPS_MAX_N = 65536
 SILHOUETTE_MAX_K = 256
+TSNE_MAX_N = 32768  # P is N^2 floats: 4 GB at the cap (csrc/tsne.hip)
+TSNE_EXPLORATION_ITERS = 250
+TSNE_EARLY_EXAGGERATION = 12.0
+TSNE_CHECK_EVERY = 50
+TSNE_MIN_GRAD_NORM = 1e-7
 
 
 # ---------------------------------------------------------------------------
@@ -217,6 +227,118 @@ class NumpyBackend:
         return sums
 
 
+    # -- exact t-SNE ------------------------------------------------------------
+    # The arithmetic of csrc/tsne.hip in fp64.  O(N^2) time per iteration and
+    # O(N^2) memory for P: meant for --device cpu on small cohorts and for the
+    # CPU tests, not as a replacement for Barnes-Hut at large N.
+    def tsne_cond_p(self, perplexity: float) -> None:
+        """P[i][j] = p(j|i) by sklearn's ``_binary_search_perplexity`` (beta from
+        1, doubled / halved until bracketed, then bisected; at most 100 steps;
+        tolerance 1e-5 on the entropy; a zero row sum counts as 1e-8), every row
+        at once.  O(N^2) per step."""
+        from scipy.spatial.distance import cdist
+
+        n = self.n
+        d2 = cdist(self.X, self.X, "sqeuclidean")
+        off = ~np.eye(n, dtype=bool)
+        target = np.log(float(perplexity))
+        tiny, tol = float(np.float32(1e-8)), float(np.float32(1e-5))  # sklearn keeps both as C floats
+        beta = np.ones(n)
+        lo = np.full(n, -np.inf)
+        hi = np.full(n, np.inf)
+        used = beta.copy()
+        sums = np.ones(n)
+        active = np.ones(n, dtype=bool)
+        for _ in range(100):
+            rows = np.flatnonzero(active)
+            if rows.size == 0:
+                break
+            b = beta[rows]
+            e = np.exp(-d2[rows] * b[:, None]) * off[rows]
+            s0 = e.sum(axis=1)
+            s0[s0 == 0.0] = tiny
+            s1 = (d2[rows] * e).sum(axis=1)
+            with np.errstate(divide="ignore"):
+                diff = np.log(s0) + b * (s1 / s0) - target
+            used[rows] = b
+            sums[rows] = s0
+            done = np.abs(diff) <= tol
+            up = (diff > 0.0) & ~done
+            down = ~up & ~done
+            r_up, r_dn = rows[up], rows[down]
+            lo[r_up] = beta[r_up]
+            beta[r_up] = np.where(np.isinf(hi[r_up]), beta[r_up] * 2.0, (beta[r_up] + hi[r_up]) / 2.0)
+            hi[r_dn] = beta[r_dn]
+            beta[r_dn] = np.where(np.isinf(lo[r_dn]), beta[r_dn] / 2.0, (beta[r_dn] + lo[r_dn]) / 2.0)
+            active[rows[done]] = False
+        self.P = np.exp(-d2 * used[:, None]) * off / sums[:, None]
+        self.beta = used
+
+    def tsne_joint_p(self) -> None:
+        """P = (P + P^T) / sum, in place of the conditional P.  O(N^2)."""
+        sym = self.P + self.P.T
+        self.P = sym / sym.sum()
+
+    def tsne_begin(self, y0: np.ndarray) -> None:
+        self.Y = np.array(y0, dtype=np.float64)
+        self.tsne_reset()
+
+    def tsne_reset(self) -> None:
+        self.upd = np.zeros_like(self.Y)
+        self.gains = np.ones_like(self.Y)
+
+    def tsne_grad(self, compute_error: bool) -> None:
+        """attr, rep, z and (when asked) the error share of every row at the
+        current Y.  O(N^2)."""
+        n, Y = self.n, self.Y
+        self.attr = np.zeros((n, 2))
+        self.rep = np.zeros((n, 2))
+        self.z = np.zeros(n)
+        self.err_rows = np.zeros(n)
+        for s, e in self._row_chunks(n):
+            dx = Y[s:e, 0, None] - Y[None, :, 0]
+            dy = Y[s:e, 1, None] - Y[None, :, 1]
+            q = 1.0 + dx * dx + dy * dy
+            w = 1.0 / q
+            w[np.arange(e - s), np.arange(s, e)] = 0.0
+            P = self.P[s:e]
+            pw, w2 = P * w, w * w
+            self.attr[s:e, 0] = (pw * dx).sum(axis=1)
+            self.attr[s:e, 1] = (pw * dy).sum(axis=1)
+            self.rep[s:e, 0] = (w2 * dx).sum(axis=1)
+            self.rep[s:e, 1] = (w2 * dy).sum(axis=1)
+            self.z[s:e] = w.sum(axis=1)
+            if compute_error:
+                pos = P > 0.0
+                self.err_rows[s:e] = np.where(pos, P * (np.log(np.where(pos, P, 1.0)) + np.log(q)), 0.0).sum(axis=1)
+
+    def tsne_step(self, exaggeration: float, momentum: float, learning_rate: float) -> None:
+        """grad = 4 (exaggeration attr - rep / Z), then sklearn's gains / momentum step."""
+        Z = float(self.z.sum())
+        grad = 4.0 * (exaggeration * self.attr - self.rep / Z)
+        self.grad = grad
+        inc = self.upd * grad < 0.0
+        self.gains = np.maximum(np.where(inc, self.gains + 0.2, self.gains * 0.8), 0.01)
+        gained = grad * self.gains
+        self.upd = momentum * self.upd - learning_rate * gained
+        self.Y = self.Y + self.upd
+        self._scalars = (Z, float(self.err_rows.sum()) + np.log(Z), float(np.sqrt((grad ** 2).sum())),
+                         float(np.sqrt((gained ** 2).sum())))
+
+    def tsne_scalars(self) -> Tuple[float, float, float, float]:
+        return self._scalars
+
+    def tsne_terms(self) -> dict:
+        return {"attr": self.attr.copy(), "rep": self.rep.copy(), "z": self.z.copy(), "err": self.err_rows.copy(),
+                "grad": self.grad.copy()}
+
+    def tsne_embedding(self) -> np.ndarray:
+        return self.Y.copy()
+
+    def tsne_p(self) -> np.ndarray:
+        return self.P.copy()
+
+
 class DeviceBackend:
     """libssip_hip.so backend (csrc/analytics.hip).  torch only owns the
     buffers and the stream; every distance is computed by the HIP kernels."""
@@ -318,6 +440,67 @@ class DeviceBackend:
         self._call("ssip_pairwise_cluster_sums", self.n, self.d, int(k), self._p(self.X), self._p(lab),
                    self._p(ordr), self._p(sums))
         return sums.cpu().numpy().astype(np.float64)
+
+
+    # -- exact t-SNE (csrc/tsne.hip) ---------------------------------------------
+    def _tsne_alloc(self) -> None:
+        t = self._torch
+        if getattr(self, "_tws", None) is not None:
+            return
+        self._tws_bytes = int(self._lib.call("ssip_tsne_workspace_bytes", self.n))
+        if self._tws_bytes < 0:
+            self._lib.check(self._tws_bytes, "ssip_tsne_workspace_bytes")
+        self._tws = t.empty(self._tws_bytes, dtype=t.uint8, device=self.dev)
+        self.P = t.empty((self.n, self.n), dtype=t.float32, device=self.dev)
+        self._beta = t.empty(self.n, dtype=t.float64, device=self.dev)
+        self._tscalars = t.empty(4, dtype=t.float64, device=self.dev)
+
+    def tsne_cond_p(self, perplexity: float) -> None:
+        self._tsne_alloc()
+        self._call("ssip_tsne_cond_p", self.n, self.d, self._p(self.X), float(perplexity), self._p(self.P),
+                   self._p(self._beta))
+
+    def tsne_joint_p(self) -> None:
+        self._call("ssip_tsne_joint_p", self.n, self._p(self.P), self._p(self._tws), self._tws_bytes)
+
+    def tsne_begin(self, y0: np.ndarray) -> None:
+        t = self._torch
+        self._tsne_alloc()
+        self.Y = t.from_numpy(np.ascontiguousarray(y0, dtype=np.float32)).to(self.dev)
+        self.upd = t.zeros_like(self.Y)
+        self.gains = t.ones_like(self.Y)
+
+    def tsne_reset(self) -> None:
+        self.upd.zero_()
+        self.gains.fill_(1.0)
+
+    def tsne_grad(self, compute_error: bool) -> None:
+        self._call("ssip_tsne_grad", self.n, self._p(self.P), self._p(self.Y), int(bool(compute_error)),
+                   self._p(self._tws), self._tws_bytes)
+
+    def tsne_step(self, exaggeration: float, momentum: float, learning_rate: float) -> None:
+        self._call("ssip_tsne_update", self.n, self._p(self._tws), self._tws_bytes, self._p(self.Y), self._p(self.upd),
+                   self._p(self.gains), float(exaggeration), float(momentum), float(learning_rate),
+                   self._p(self._tscalars))
+
+    def tsne_scalars(self) -> Tuple[float, float, float, float]:
+        s = self._tscalars.cpu().numpy()  # the one read-back, on error iterations only
+        return float(s[0]), float(s[1]), float(s[2]), float(s[3])
+
+    def tsne_terms(self) -> dict:
+        """Row sums and gradient of the last grad + step, from the workspace (include/ssip.h)."""
+        n = self.n
+        head = ((4 * ((n + 255) // 256) + 1) * 8 + 15) // 16 * 16
+        raw = self._tws[head:head + 8 * n * 4].cpu().numpy().view(np.float32)
+        red = raw[:6 * n].reshape(6, n)
+        return {"attr": red[0:2].T.copy(), "rep": red[2:4].T.copy(), "z": red[4].copy(), "err": red[5].copy(),
+                "grad": raw[6 * n:].reshape(n, 2).copy()}
+
+    def tsne_embedding(self) -> np.ndarray:
+        return self.Y.cpu().numpy()
+
+    def tsne_p(self) -> np.ndarray:
+        return self.P.cpu().numpy()
 
 
 def make_backend(X: np.ndarray, device: str = "cuda"):
@@ -428,3 +611,73 @@ def kth_neighbor_distance(X: np.ndarray, k: int, device: str = "cuda", backend=N
         raise ValueError(f"ssip.analytics: Expected n_neighbors <= n_samples, but n_neighbors = {k}, n_samples = {n}")
     backend = backend if backend is not None else make_backend(X, device)
     return backend.kth(int(k))
+
+
+def tsne_init(X: np.ndarray, seed: int) -> np.ndarray:
+    """sklearn's init="pca": the first two randomized-PCA components as
+    float32, scaled so that the first has standard deviation 1e-4."""
+    from sklearn.decomposition import PCA
+
+    emb = PCA(n_components=2, svd_solver="randomized", random_state=seed).fit_transform(X).astype(np.float32,
+                                                                                                  copy=False)
+    return emb / np.std(emb[:, 0]) * 1e-4
+
+
+def tsne_fit(X: np.ndarray, perplexity: float, seed: int = 42, max_iter: int = 1000, device: str = "cuda",
+             backend=None):
+    """(embedding float32 [N][2], kl_divergence, n_iter) of exact t-SNE under
+    sklearn's schedule (``_t_sne.py``: ``TSNE._tsne`` and ``_gradient_descent``):
+    PCA init, learning rate max(N / 48, 50), early exaggeration 12 with
+    momentum 0.5 up to iteration 250 and then 1 / 0.8, ``update`` and ``gains``
+    reset at the start of each phase, the error taken on every 50th iteration
+    and on the last of a phase, a stop when it has not improved for more than
+    300 iterations (250 in the first phase) or when the norm of the gained
+    gradient is <= 1e-7.  A stop in the first phase starts the second one, as
+    in sklearn.  ``kl_divergence`` is that of the unexaggerated P at the last
+    iterate the gradient was taken at; ``n_iter`` counts the steps taken.
+
+    The scalars are read back on the error iterations only; nothing else
+    synchronises host and device inside the loop."""
+    X = np.asarray(X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    n = X.shape[0]
+    if not 2 <= n <= TSNE_MAX_N:
+        raise ValueError(f"ssip.analytics: exact t-SNE supports 2 <= N <= {TSNE_MAX_N} (got {n}): P is N^2 floats")
+    if not 0.0 < float(perplexity) < n:
+        raise ValueError(f"ssip.analytics: perplexity {perplexity} must be positive and less than n_samples = {n}")
+    backend = backend if backend is not None else make_backend(X, device)
+    learning_rate = max(n / TSNE_EARLY_EXAGGERATION / 4.0, 50.0)
+    backend.tsne_cond_p(float(perplexity))
+    backend.tsne_joint_p()
+    backend.tsne_begin(tsne_init(X, seed))
+
+    max_iter = int(max_iter)
+    phases = ((min(TSNE_EXPLORATION_ITERS, max_iter), TSNE_EARLY_EXAGGERATION, 0.5, TSNE_EXPLORATION_ITERS),
+              (max_iter, 1.0, 0.8, MAX_ITER))
+    start, last, kl = 0, -1, float("nan")
+    for end, exaggeration, momentum, patience in phases:
+        if start >= end:
+            continue
+        backend.tsne_reset()
+        best_err, best_it = np.finfo(float).max, start
+        for i in range(start, end):
+            check = (i + 1) % TSNE_CHECK_EVERY == 0
+            want_err = check or i == end - 1
+            backend.tsne_grad(want_err)
+            backend.tsne_step(exaggeration, momentum, learning_rate)
+            last = i
+            if not want_err:
+                continue
+            _, kl, _, gained_norm = backend.tsne_scalars()
+            if not check:
+                continue
+            err = exaggeration * (kl + np.log(exaggeration))  # the KL of exaggeration * P, as sklearn tracks it
+            if err < best_err:
+                best_err, best_it = err, i
+            elif i - best_it > patience:
+                break
+            if gained_norm <= TSNE_MIN_GRAD_NORM:
+                break
+        start = last + 1
+    return backend.tsne_embedding().astype(np.float32), float(kl), last + 1
