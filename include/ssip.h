@@ -27,6 +27,8 @@
  *     -> ssip_kmeans_assign / _update, ssip_pairwise_eps / _kth / _cluster_sums
  *   TSNE(...).fit_transform                  src/clustering.py:251-276
  *     -> ssip_tsne_cond_p / _joint_p / _grad / _update (the exact objective)
+ *   umap.UMAP(...).fit_transform             src/clustering.py:279-306
+ *     -> ssip_knn, ssip_umap_fuzzy, ssip_umap_epoch (exact kNN, Jacobi epochs)
  *
  * Conventions
  *   - Every pointer is a device pointer unless documented otherwise; the
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define SSIP_ABI_VERSION 16
+#define SSIP_ABI_VERSION 17
 
 enum ssip_dtype { SSIP_F32 = 0, SSIP_BF16 = 1 };
 enum ssip_status { SSIP_OK = 0, SSIP_ERR_ARG = -1, SSIP_ERR_LAUNCH = -2, SSIP_ERR_WORKSPACE = -3 };
@@ -477,6 +479,85 @@ int ssip_tsne_grad(int N, const float* P, const float* Y, int compute_error, voi
  * [N][2]. */
 int ssip_tsne_update(int N, void* workspace, int64_t workspace_bytes, float* Y, float* update, float* gains,
                      float exaggeration, float momentum, float learning_rate, double* scalars, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Native UMAP (reference src/clustering.py:279-306 run_umap, which calls
+ * umap.UMAP(n_components=2, metric="euclidean")): exact k nearest neighbours,
+ * umap-learn's smooth_knn_dist / membership strengths, and one epoch of its
+ * layout optimisation in Jacobi order.  The graph symmetrisation, the a / b
+ * curve fit, the schedule and the initial layout stay on the host
+ * (ssip/analytics.py).  fp32 unless said otherwise, no atomics, every
+ * reduction in a fixed order (bit-reproducible).  2 <= N <= 2^20.
+ * ---------------------------------------------------------------------- */
+/* d2[i][c], idx[i][c] (both [N][k]) = the k smallest squared distances from
+ * row i of X (fp32 [N][d], 1 <= d <= 512; direct difference, feature order, as
+ * the analytics section) to any row, self included, ascending, with their
+ * column indices; equal distances are ordered by index.  2 <= k <= min(64, N).
+ * The first k' columns of a k result are the k' result bit for bit. */
+int ssip_knn(int N, int d, int k, const float* X, float* d2, int32_t* idx, void* stream);
+/* bytes of the workspace of ssip_umap_fuzzy: per-row distance sums (fp64 [N])
+ * and their total */
+int64_t ssip_umap_workspace_bytes(int64_t N);
+/* umap-learn's smooth_knn_dist and compute_membership_strengths over the first
+ * k columns of a kNN result of leading dimension ld >= k (d2 and idx as
+ * ssip_knn wrote them; distances are sqrt(d2) rounded to fp32).  Per row:
+ * rho[i] = the smallest non-zero distance, or 0; sigma[i] by bisection (lo 0,
+ * mid 1 doubled until bracketed, at most 64 steps) until |sum_{c >= 1} (d_c -
+ * rho > 0 ? exp(-(d_c - rho) / sigma) : 1) - log2 k| < 1e-5, then floored at
+ * 1e-3 x the row's mean distance (rho > 0) or the mean of all N * k distances
+ * (rho = 0).  memb[i][c] ([N][k]) = 0 where idx[i][c] == i, 1 where d_c - rho
+ * <= 0 or sigma = 0, else exp(-(d_c - rho) / sigma).  exp and all sums are
+ * fp64; the global mean is reduced per row, then over the rows in a fixed
+ * order.  2 <= k <= 64.  The workspace must be 16-byte aligned. */
+int ssip_umap_fuzzy(int N, int k, int ld, const float* d2, const int32_t* idx, float* rho, float* sigma, float* memb,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* The vertex negative sampling draws for (seed, epoch n, CSR edge e, draw p) is
+ * ssip_umap_hash(seed, n, e, p) % N: a counter-based integer hash, a pure
+ * function of its four arguments (ssip/analytics.py restates it with numpy
+ * integers). */
+#if defined(__HIP__)
+#define SSIP_HOST_DEVICE __attribute__((host)) __attribute__((device))
+#else
+#define SSIP_HOST_DEVICE
+#endif
+static inline SSIP_HOST_DEVICE uint32_t ssip_umap_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+static inline SSIP_HOST_DEVICE uint32_t ssip_umap_hash(uint32_t seed, uint32_t n, uint32_t e, uint32_t p) {
+  uint32_t h = ssip_umap_mix(seed * 0x9e3779b1u + n);
+  h = ssip_umap_mix(h ^ e);
+  return ssip_umap_mix(h + p * 0x85ebca77u);
+}
+/* Epoch n of umap-learn's optimize_layout_euclidean in Jacobi order: every
+ * vertex reads y_in (fp32 [N][2]) and writes y_out (which must not alias it).
+ * The graph is CSR (row_ptr int32 [N + 1], col int32 [E]) holding both
+ * directions of every edge with identical eps (epochs per sample, fp32 [E]);
+ * epn = epochs per negative sample.  For vertex i and each edge e = (i, j) of
+ * its row with next_sample[e] <= n:
+ *   attraction  c = -2ab d2^(b-1) / (a d2^b + 1) for d2 = |y_i - y_j|^2 > 0,
+ *               else 0; add 2 clip(c (y_i - y_j), +-4) per coordinate (the
+ *               factor 2 is the twin edge's move_other update of i);
+ *               next_sample[e] += eps[e];
+ *   repulsion   n_neg = int((n - next_neg[e]) / epn[e]); for p < n_neg the
+ *               vertex k = ssip_umap_hash(seed, n, e, p) % N; k == i or d2 == 0
+ *               adds nothing, else c = 2 gamma b / ((0.001 + d2)(a d2^b + 1)),
+ *               add clip(c (y_i - y_k), +-4); next_neg[e] += n_neg * epn[e].
+ *               eps >= 1 (it is max w / w), which keeps n_neg <= 5 n; n_neg is
+ *               clamped to 0..65536.  An endpoint outside 0..N-1 is skipped.
+ * y_out[i] = y_in[i] + alpha * sum, the forces and the sum in fp64, rounded to
+ * fp32 once.  One wave per vertex: lanes stride the row, each summing its
+ * edges in order, then a fixed butterfly.  The state
+ * updates and the n_neg expression are fp32 operations rounded one by one (no
+ * contraction), so numpy's float32 arithmetic gives the same bits; each edge's
+ * state is touched by the one lane that owns it. */
+int ssip_umap_epoch(int N, const int32_t* row_ptr, const int32_t* col, const float* eps, const float* epn,
+                    float* next_sample, float* next_neg, const float* y_in, float* y_out, float a, float b,
+                    float gamma, float alpha, int n, uint32_t seed, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the stream-ordered entry points

@@ -1,0 +1,365 @@
+// Native UMAP (reference src/clustering.py:279-306, which calls umap.UMAP):
+// the three device stages of ssip.analytics.umap_fit.  The algorithm is
+// umap-learn's (nearest neighbours -> smooth_knn_dist -> membership strengths
+// -> optimize_layout_euclidean); the graph symmetrisation, the a / b curve
+// fit, the schedule and the initial layout are O(N k) host work.
+//
+// Everything is fp32 unless said otherwise.  No atomics; every reduction runs
+// in a fixed order, so all outputs are bit-reproducible from run to run.
+//
+//   knn:    layout A of analytics.hip (pairwise_tile.h), the walk of
+//           pairwise_a_kernel<1>.  A candidate is one 64-bit key, the bits of
+//           the squared distance above the column index: d2 >= 0, so keys order
+//           by distance and then by index, and no two keys are equal.  Each of
+//           a wave's 16 rows keeps its 64 smallest keys ascending, one per
+//           lane; a column tile is merged in (bitonic sort + bitonic merge)
+//           only when one of its keys is below the row's current k-th key.
+//   fuzzy:  one wave per row, lane = neighbour column.  rho by a wave minimum,
+//           sigma by umap's bisection with exp and the sums in fp64.  The mean
+//           of all distances (the sigma floor of rows with rho = 0) is reduced
+//           per row, then over the rows by one workgroup in index order.
+//   epoch:  one wave per vertex, lanes stride over its CSR row.  Epochs are
+//           Jacobi-ordered (read y_in, write y_out), so no vertex sees a
+//           half-updated neighbour and the result does not depend on the
+//           order the waves run in.  A lane owns the schedule state of the
+//           edges it visits; the forces and the per-vertex sum (the lanes'
+//           running sums through a fixed butterfly) are fp64, then one plain
+//           8-byte store of the fp32 position.
+#include "ssip_common.h"
+#include "pairwise_tile.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int UMAP_MAX_N = 1 << 20;
+constexpr int KNN_MAX_K = 64;
+constexpr int FIN_NT = 256;         // global mean: one workgroup
+constexpr int BISECT_STEPS = 64;    // umap's n_iter
+constexpr int MAX_NEG = 65536;      // draws of one edge in one epoch (eps >= 1 gives n_neg <= 5 n)
+typedef unsigned long long u64;
+
+// ---------------------------------------------------------------------------
+// exact kNN
+// ---------------------------------------------------------------------------
+// ascending bitonic sort of one key per lane across the wave
+__device__ __forceinline__ u64 wave_sort_key(u64 v, int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const u64 p = __shfl_xor(v, j, 64);
+      const bool up = (lane & k) == 0;
+      const bool lo = (lane & j) == 0;
+      v = (lo == up) ? (p < v ? p : v) : (p > v ? p : v);
+    }
+  }
+  return v;
+}
+// best: ascending 64 smallest so far; cand: 64 new keys.  Returns the
+// ascending 64 smallest of the union.
+__device__ __forceinline__ u64 wave_merge_smallest_key(u64 best, u64 cand, int lane) {
+  const u64 s = wave_sort_key(cand, lane);
+  const u64 r = __shfl(s, 63 - lane, 64);
+  u64 m = r < best ? r : best;  // bitonic, holds the 64 smallest
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const u64 p = __shfl_xor(m, j, 64);
+    m = (lane & j) == 0 ? (p < m ? p : m) : (p > m ? p : m);
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(NT) void knn_kernel(int N, int d, int kk, const float* __restrict__ X,
+                                                 float* __restrict__ d2out, int32_t* __restrict__ idxout) {
+  __shared__ __attribute__((aligned(16))) float xr[DC * XR_LD];
+  __shared__ float xc[64 * XC_LD];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int row0 = blockIdx.x * RA;
+  const int nch = (d + DC - 1) / DC, ntile = (N + 63) / 64;
+
+  u64 best[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) best[u] = ~0ull;
+
+  float pre_r[TQ], pre_c[TQ];
+  fetch_tile_a(pre_r, X, row0, N, d, 0, tid);
+  fetch_tile_a(pre_c, X, 0, N, d, 0, tid);
+  float acc[16];
+  const int steps = ntile * nch;
+  for (int it = 0; it < steps; ++it) {
+    const int jt = it / nch, ch = it - jt * nch;
+    // a single-chunk row tile stays resident for the whole column walk
+    if (nch > 1 || it == 0) put_rows_a(xr, pre_r, tid);
+    put_cols_a(xc, pre_c, tid);
+    __syncthreads();
+    if (it + 1 < steps) {  // next step's tiles, in flight during the arithmetic below
+      const int jn = (it + 1) / nch, cn = (it + 1) - jn * nch;
+      if (nch > 1) fetch_tile_a(pre_r, X, row0, N, d, cn * DC, tid);
+      fetch_tile_a(pre_c, X, jn * 64, N, d, cn * DC, tid);
+    }
+    if (ch == 0) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) acc[u] = 0.f;
+    }
+    accumulate_a(acc, xr, xc, w, lane);
+    __syncthreads();
+    if (ch != nch - 1) continue;
+    const int j = jt * 64 + lane;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const u64 cand = j < N ? ((u64)__float_as_uint(acc[u]) << 32) | (u64)(uint32_t)j : ~0ull;
+      const u64 thr = __shfl(best[u], kk - 1, 64);
+      if (__any(cand < thr)) best[u] = wave_merge_smallest_key(best[u], cand, lane);  // wave-uniform branch
+    }
+  }
+  // k <= N, so the first k keys of every row are real candidates
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int i = row0 + w * 16 + u;
+    if (i < N && lane < kk) {
+      d2out[(long)i * kk + lane] = __uint_as_float((uint32_t)(best[u] >> 32));
+      idxout[(long)i * kk + lane] = (int32_t)(uint32_t)(best[u] & 0xffffffffull);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// smooth_knn_dist + membership strengths
+// ---------------------------------------------------------------------------
+struct UmapWs {
+  double* rowsum;  // [N] sum of the row's k distances
+  double* total;   // [1] sum of rowsum in index order
+};
+inline long umap_ws_bytes(long N) { return (N + 1) * 8 + 8; }
+inline UmapWs umap_ws(void* base, long N) {
+  UmapWs ws;
+  ws.rowsum = static_cast<double*>(base);
+  ws.total = ws.rowsum + N;
+  return ws;
+}
+
+// the distance umap sees: sqrt of the kNN squared distance, rounded to fp32
+// once (the fp64 root of an fp32 value rounds to the correctly rounded fp32 root)
+__device__ __forceinline__ float knn_dist(float d2) { return (float)sqrt((double)d2); }
+
+// wave = row, lane = column
+__global__ __launch_bounds__(NT) void umap_rowsum_kernel(int N, int k, int ld, const float* __restrict__ d2,
+                                                         double* __restrict__ rowsum) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (i >= N) return;  // wave-uniform
+  const double v = lane < k ? (double)knn_dist(d2[(long)i * ld + lane]) : 0.0;
+  const double s = wave_sum_d(v);
+  if (lane == 0) rowsum[i] = s;
+}
+
+// One workgroup: total = sum of rowsum, thread-strided, then wave butterfly,
+// then the waves in order
+__global__ __launch_bounds__(FIN_NT) void umap_total_kernel(int N, const double* __restrict__ rowsum,
+                                                            double* __restrict__ total) {
+  __shared__ double slot[FIN_NT / 64];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int q = tid; q < N; q += FIN_NT) s += rowsum[q];
+  s = wave_sum_d(s);
+  if ((tid & 63) == 0) slot[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < FIN_NT / 64; ++q) t += slot[q];
+    *total = t;
+  }
+}
+
+__global__ __launch_bounds__(NT) void umap_fuzzy_kernel(int N, int k, int ld, const float* __restrict__ d2,
+                                                        const int32_t* __restrict__ idx, UmapWs ws,
+                                                        float* __restrict__ rho_out, float* __restrict__ sigma_out,
+                                                        float* __restrict__ memb) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (i >= N) return;  // wave-uniform
+  const bool in = lane < k;
+  const float dist = in ? knn_dist(d2[(long)i * ld + lane]) : 0.f;
+
+  float m = (in && dist > 0.f) ? dist : INFINITY;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+  const float rho = m == INFINITY ? 0.f : m;
+
+  const double target = log2((double)k);
+  const double dd = (double)dist - (double)rho;
+  const bool counted = in && lane >= 1;
+  double lo = 0.0, hi = INFINITY, mid = 1.0;
+  for (int l = 0; l < BISECT_STEPS; ++l) {
+    const double term = counted ? (dd > 0.0 ? exp(-dd / mid) : 1.0) : 0.0;
+    const double psum = wave_sum_d(term);  // the same bits in every lane
+    if (fabs(psum - target) < 1e-5) break;
+    if (psum > target) {
+      hi = mid;
+      mid = (lo + hi) / 2.0;
+    } else {
+      lo = mid;
+      mid = hi == INFINITY ? mid * 2.0 : (lo + hi) / 2.0;
+    }
+  }
+  const double mean = rho > 0.f ? ws.rowsum[i] / (double)k : *ws.total / ((double)N * (double)k);
+  if (mid < 1e-3 * mean) mid = 1e-3 * mean;
+
+  if (in) {
+    float v;
+    if (idx[(long)i * ld + lane] == i)
+      v = 0.f;
+    else if (dd <= 0.0 || mid == 0.0)
+      v = 1.f;
+    else
+      v = (float)exp(-dd / mid);
+    memb[(long)i * k + lane] = v;
+  }
+  if (lane == 0) {
+    rho_out[i] = rho;
+    sigma_out[i] = (float)mid;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// layout epoch
+// ---------------------------------------------------------------------------
+// The schedule of one firing edge: next_sample += eps; n_neg = int((n -
+// next_neg) / epn); next_neg += n_neg * epn.  Contraction is off: every
+// operation is rounded to fp32 on its own, as numpy rounds them, so an fma
+// must not replace the multiply and the add.
+__device__ __forceinline__ int umap_schedule(float nf, float eps, float epn, float& next_sample, float& next_neg) {
+#pragma clang fp contract(off)
+  next_sample = next_sample + eps;
+  const float ahead = nf - next_neg;
+  const float q = ahead / epn;
+  int m = (int)q;
+  m = m < 0 ? 0 : (m > MAX_NEG ? MAX_NEG : m);
+  const float adv = (float)m * epn;
+  next_neg = next_neg + adv;
+  return m;
+}
+
+__device__ __forceinline__ double clip4(double v) { return fmin(fmax(v, -4.0), 4.0); }
+
+// Positions and the schedule state are fp32; the forces and their sum are
+// fp64.  The map is sensitive (a repulsion near contact has a slope in the
+// hundreds per unit of distance), so a rounding error of fp32 forces grows
+// about tenfold per epoch, and a hub's fp32 sum of a hundred clipped terms
+// starts it off well above the rounding of the positions themselves.
+__global__ __launch_bounds__(NT) void umap_epoch_kernel(int N, const int32_t* __restrict__ row_ptr,
+                                                        const int32_t* __restrict__ col,
+                                                        const float* __restrict__ eps, const float* __restrict__ epn,
+                                                        float* __restrict__ next_sample,
+                                                        float* __restrict__ next_neg, const float* __restrict__ y_in,
+                                                        float* __restrict__ y_out, float a32, float b32, float gamma,
+                                                        float alpha, int n, uint32_t seed) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (i >= N) return;  // wave-uniform
+  const double yix = (double)y_in[2 * (long)i], yiy = (double)y_in[2 * (long)i + 1];
+  const int e0 = row_ptr[i], e1 = row_ptr[i + 1];
+  const float nf = (float)n;
+  const double a = (double)a32, b = (double)b32;
+  const double attr_scale = -2.0 * a * b, rep_scale = 2.0 * (double)gamma * b;
+
+  double fx = 0.0, fy = 0.0;
+  for (int e = e0 + lane; e < e1; e += 64) {
+    float ns = next_sample[e];
+    if (!(ns <= nf)) continue;
+    const int j = col[e];
+    if ((unsigned)j >= (unsigned)N) continue;  // never read outside y_in
+    {
+      const double dx = yix - (double)y_in[2 * (long)j], dy = yiy - (double)y_in[2 * (long)j + 1];
+      const double d2 = dx * dx + dy * dy;
+      if (d2 > 0.0) {
+        const double pb = pow(d2, b);
+        const double c = attr_scale * (pb / d2) / (a * pb + 1.0);
+        fx += 2.0 * clip4(c * dx);
+        fy += 2.0 * clip4(c * dy);
+      }
+    }
+    float nn = next_neg[e];
+    const int n_neg = umap_schedule(nf, eps[e], epn[e], ns, nn);
+    next_sample[e] = ns;
+    next_neg[e] = nn;
+    for (int p = 0; p < n_neg; ++p) {
+      const int k = (int)(ssip_umap_hash(seed, (uint32_t)n, (uint32_t)e, (uint32_t)p) % (uint32_t)N);
+      if (k == i) continue;
+      const double dx = yix - (double)y_in[2 * (long)k], dy = yiy - (double)y_in[2 * (long)k + 1];
+      const double d2 = dx * dx + dy * dy;
+      if (d2 > 0.0) {
+        const double pb = pow(d2, b);
+        const double c = rep_scale / ((0.001 + d2) * (a * pb + 1.0));
+        fx += clip4(c * dx);
+        fy += clip4(c * dy);
+      }
+    }
+  }
+  fx = wave_sum_d(fx);
+  fy = wave_sum_d(fy);
+  if (lane == 0) {
+    float2 o;
+    o.x = (float)(yix + (double)alpha * fx);
+    o.y = (float)(yiy + (double)alpha * fy);
+    *reinterpret_cast<float2*>(y_out + 2 * (long)i) = o;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssip_knn(int N, int d, int k, const float* X, float* d2, int32_t* idx, void* stream) {
+  SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_knn: N = %d outside 2..%d", N, UMAP_MAX_N);
+  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "ssip_knn: d = %d outside 1..512", d);
+  SSIP_REQUIRE(k >= 2 && k <= KNN_MAX_K, SSIP_ERR_ARG, "ssip_knn: k = %d outside 2..%d", k, KNN_MAX_K);
+  SSIP_REQUIRE(k <= N, SSIP_ERR_ARG, "ssip_knn: k = %d neighbours asked of N = %d points", k, N);
+  SSIP_REQUIRE(X && d2 && idx, SSIP_ERR_ARG, "ssip_knn: null pointer");
+  SSIP_KLAUNCH(knn_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, k, X, d2, idx);
+  return ssip::check_launch("ssip_knn");
+}
+
+int64_t ssip_umap_workspace_bytes(int64_t N) {
+  SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_umap_workspace_bytes: N = %ld outside 2..%d", (long)N,
+               UMAP_MAX_N);
+  return umap_ws_bytes(N);
+}
+
+int ssip_umap_fuzzy(int N, int k, int ld, const float* d2, const int32_t* idx, float* rho, float* sigma, float* memb,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_umap_fuzzy: N = %d outside 2..%d", N, UMAP_MAX_N);
+  SSIP_REQUIRE(k >= 2 && k <= KNN_MAX_K && k <= N, SSIP_ERR_ARG, "ssip_umap_fuzzy: k = %d outside 2..min(%d, N = %d)",
+               k, KNN_MAX_K, N);
+  SSIP_REQUIRE(ld >= k, SSIP_ERR_ARG, "ssip_umap_fuzzy: leading dimension %d below k = %d", ld, k);
+  SSIP_REQUIRE(d2 && idx && rho && sigma && memb, SSIP_ERR_ARG, "ssip_umap_fuzzy: null pointer");
+  SSIP_REQUIRE(workspace != nullptr, SSIP_ERR_ARG, "ssip_umap_fuzzy: null workspace");
+  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
+               "ssip_umap_fuzzy: workspace must be 16-byte aligned");
+  SSIP_REQUIRE(workspace_bytes >= umap_ws_bytes(N), SSIP_ERR_WORKSPACE,
+               "ssip_umap_fuzzy: workspace of %ld bytes, need %ld", (long)workspace_bytes, umap_ws_bytes(N));
+  const UmapWs ws = umap_ws(workspace, N);
+  const dim3 grid((N + NT / 64 - 1) / (NT / 64));
+  SSIP_KLAUNCH(umap_rowsum_kernel, grid, dim3(NT), 0, (hipStream_t)stream, N, k, ld, d2, ws.rowsum);
+  SSIP_KLAUNCH(umap_total_kernel, dim3(1), dim3(FIN_NT), 0, (hipStream_t)stream, N, ws.rowsum, ws.total);
+  SSIP_KLAUNCH(umap_fuzzy_kernel, grid, dim3(NT), 0, (hipStream_t)stream, N, k, ld, d2, idx, ws, rho, sigma, memb);
+  return ssip::check_launch("ssip_umap_fuzzy");
+}
+
+int ssip_umap_epoch(int N, const int32_t* row_ptr, const int32_t* col, const float* eps, const float* epn,
+                    float* next_sample, float* next_neg, const float* y_in, float* y_out, float a, float b,
+                    float gamma, float alpha, int n, uint32_t seed, void* stream) {
+  SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_umap_epoch: N = %d outside 2..%d", N, UMAP_MAX_N);
+  SSIP_REQUIRE(row_ptr && col && eps && epn && next_sample && next_neg && y_in && y_out, SSIP_ERR_ARG,
+               "ssip_umap_epoch: null pointer");
+  SSIP_REQUIRE(y_in != y_out, SSIP_ERR_ARG, "ssip_umap_epoch: y_out must not alias y_in (epochs are Jacobi-ordered)");
+  SSIP_REQUIRE(n >= 0 && n < (1 << 24), SSIP_ERR_ARG, "ssip_umap_epoch: epoch %d outside 0..2^24 - 1", n);
+  SSIP_REQUIRE(a > 0.f && b > 0.f, SSIP_ERR_ARG, "ssip_umap_epoch: a = %g, b = %g must be > 0", (double)a, (double)b);
+  SSIP_KLAUNCH(umap_epoch_kernel, dim3((N + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, N, row_ptr,
+               col, eps, epn, next_sample, next_neg, y_in, y_out, a, b, gamma, alpha, n, seed);
+  return ssip::check_launch("ssip_umap_epoch");
+}
+
+}  // extern "C"

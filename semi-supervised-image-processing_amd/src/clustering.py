@@ -18,7 +18,7 @@ What runs where:
     the k-distance curve (:430-438, :541-563) go through ssip.analytics.
     ``--device cuda`` (and ``auto``) uses the HIP kernels; ``--device cpu`` is
     an explicit host path on the same driver with the numpy backend.  Two
-    extension flags: ``--device`` and ``--tsne-method``.
+    extension flags: ``--device``, ``--tsne-method`` and ``--umap-method``.
   * Standardisation checks and PCA (sklearn, svd_solver="full": the reference's
     cluster space bit for bit) stay on the host: O(N*D^2) at most, against
     O(N^2*d) per DBSCAN / silhouette configuration.
@@ -26,10 +26,16 @@ What runs where:
     ``--tsne-method exact`` runs the exact objective under sklearn's schedule
     through ssip.analytics.tsne_fit (csrc/tsne.hip) on the resolved --device,
     with the same artefact names, npz keys and params.
-  * UMAP runs through ``umap`` when that package imports; when it does not, one
-    warning is logged and the UMAP grid is empty, for which the assignments
-    table names pca_2d as umap_id (the reference's behaviour for an empty grid,
-    :858).
+  * UMAP by default (``--umap-method package``) runs through ``umap`` when that
+    package imports; when it does not, one warning is logged and the UMAP grid
+    is empty, for which the assignments table names pca_2d as umap_id (the
+    reference's behaviour for an empty grid, :858).  ``--umap-method native``
+    needs no package: ssip.analytics.umap_fit (csrc/umap.hip) on the resolved
+    --device, exact kNN computed once at the largest n_neighbors, the
+    reference's artefact names, npz keys and params.  An n_neighbors above
+    min(64, N) is skipped with a warning.  The embeddings are reproducible bit
+    for bit but not comparable point for point with umap-learn's (Jacobi-ordered
+    epochs, hashed negative samples).
 """
 from __future__ import annotations
 
@@ -54,6 +60,7 @@ ASSIGNMENT_COLUMNS = ("path", "cluster_kmeans", "cluster_dbscan", "pca_dim", "ts
                       "true_label")
 SCOPES = ("all", "labeled", "unlabeled")
 TSNE_METHODS = ("barnes_hut", "exact")
+UMAP_METHODS = ("package", "native")
 
 
 @dataclass(frozen=True)
@@ -196,10 +203,41 @@ def run_tsne(base: EmbeddingResult, perplexities: Sequence[float], seed: int, me
     return out
 
 
+def run_umap_native(base: EmbeddingResult, neighbor_values: Sequence[int], min_dists: Sequence[float], seed: int,
+                    device: str) -> List[EmbeddingResult]:
+    """ssip.analytics.umap_fit for every (n_neighbors, min_dist); the kNN graph
+    is built once at the largest n_neighbors and sliced."""
+    n = base.data.shape[0]
+    cap = min(analytics.KNN_MAX_K, n)
+    usable = [int(nn) for nn in neighbor_values if 2 <= int(nn) <= cap]
+    skipped = [int(nn) for nn in neighbor_values if not 2 <= int(nn) <= cap]
+    if skipped:
+        logging.warning("native UMAP supports 2 <= n_neighbors <= min(%s, N = %s): skipping n_neighbors = %s",
+                        analytics.KNN_MAX_K, n, skipped)
+    if not usable:
+        return []
+    backend = analytics.make_backend(base.data, device)
+    backend.knn(max(usable))
+    out = []
+    for nn in usable:
+        for md in min_dists:
+            logging.info("Running UMAP (n_neighbors=%s, min_dist=%.2f, method=native)", nn, md)
+            emb, _ = analytics.umap_fit(base.data, nn, float(md), seed=seed, device=device, backend=backend)
+            out.append(EmbeddingResult(f"umap_nn{int(nn)}_md{md:.2f}", emb,
+                                       {"n_neighbors": int(nn), "min_dist": float(md), "seed": seed}))
+    return out
+
+
 def run_umap(base: EmbeddingResult, neighbor_values: Sequence[int], min_dists: Sequence[float],
-             seed: int) -> List[EmbeddingResult]:
+             seed: int, method: str = "package", device: str = "cuda") -> List[EmbeddingResult]:
+    """package: the reference's ``umap`` call (an empty grid and one warning
+    when the package does not import).  native: ssip.analytics.umap_fit."""
+    if method not in UMAP_METHODS:
+        raise ValueError("UMAP method must be one of: " + ", ".join(UMAP_METHODS))
     if not neighbor_values or not min_dists:
         return []
+    if method == "native":
+        return run_umap_native(base, neighbor_values, min_dists, seed, device)
     try:
         import umap  # type: ignore
     except ImportError:
@@ -451,6 +489,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--tsne-method", type=str, default="barnes_hut", choices=list(TSNE_METHODS),
                    help="barnes_hut = sklearn's TSNE on the host (the reference's call); exact = the exact objective "
                         "through ssip.analytics.tsne_fit on --device.")
+    p.add_argument("--umap-method", type=str, default="package", choices=list(UMAP_METHODS),
+                   help="package = the umap package on the host (the reference's call; skipped with a warning when "
+                        "it is not installed); native = ssip.analytics.umap_fit on --device, no package needed.")
     return p.parse_args(argv)
 
 
@@ -468,7 +509,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     pca = run_pca(bundle.features, args.variance_target, args.tsne_dim, args.seed)
     emb_dir = args.output_root / "features" / "dimensionality_reduction"
     tsne = run_tsne(pca.pca_tsne_init, args.tsne_perplexities, args.seed, args.tsne_method, device)
-    umaps = run_umap(pca.pca_tsne_init, args.umap_neighbors, args.umap_min_dist, args.seed)
+    umaps = run_umap(pca.pca_tsne_init, args.umap_neighbors, args.umap_min_dist, args.seed, args.umap_method, device)
     for emb in [pca.cluster_space, pca.pca_2d, pca.pca_tsne_init, *tsne, *umaps]:
         save_embedding_npz(emb_dir, emb)
 

@@ -29,7 +29,7 @@ def abi_version_expected() -> int:
     return int(m.group(1)) if m else ABI_VERSION
 
 
-ABI_VERSION = 16  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
+ABI_VERSION = 17  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
 
 F32 = 0
 BF16 = 1
@@ -150,6 +150,11 @@ _SIGS = {
     "ssip_tsne_joint_p": (_c_int, [_c_int, _vp, _vp, _c_i64, _vp]),
     "ssip_tsne_grad": (_c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_i64, _vp]),
     "ssip_tsne_update": (_c_int, [_c_int, _vp, _c_i64, _vp, _vp, _vp, _c_f, _c_f, _c_f, _vp, _vp]),
+    # native UMAP (ssip/analytics.py)
+    "ssip_knn": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "ssip_umap_workspace_bytes": (_c_i64, [_c_i64]),
+    "ssip_umap_fuzzy": (_c_int, [_c_int, _c_int, _c_int] + [_vp] * 6 + [_c_i64, _vp]),
+    "ssip_umap_epoch": (_c_int, [_c_int] + [_vp] * 8 + [_c_f] * 4 + [_c_int, ctypes.c_uint32, _vp]),
     # launch plans (ssip/plan.py)
     "ssip_plan_create": (_vp, []),
     "ssip_plan_destroy": (None, [_vp]),

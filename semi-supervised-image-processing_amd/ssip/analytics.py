@@ -21,6 +21,10 @@ csrc/analytics.hip; what stays on the host is the control flow around them:
   sklearn's two-phase schedule of gradient and momentum / gains steps with one
   read-back of four scalars on every 50th iteration and nothing else crossing
   the bus.
+* ``umap_fit`` is umap-learn's algorithm with its own kernels (csrc/umap.hip):
+  exact kNN, ``smooth_knn_dist`` and the membership strengths on the backend,
+  the fuzzy union / curve fit / schedule / init on the host (O(N k)), then the
+  layout epochs on the backend in Jacobi order with hashed negative samples.
 
 The Lloyd driver and the DBSCAN labeller work on a small backend object
 (``assign`` / ``update`` / ``eps_graph`` / ...).  ``DeviceBackend`` launches
@@ -30,6 +34,7 @@ without a GPU.  Nothing here falls back from one to the other.
 """
 from __future__ import annotations
 
+import logging
 from typing import Optional, Tuple
 
 import numpy as np
@@ -44,6 +49,11 @@ TSNE_EXPLORATION_ITERS = 250
 TSNE_EARLY_EXAGGERATION = 12.0
 TSNE_CHECK_EVERY = 50
 TSNE_MIN_GRAD_NORM = 1e-7
+KNN_MAX_K = 64
+UMAP_MAX_N = 1 << 20
+UMAP_NEGATIVE_SAMPLE_RATE = 5
+UMAP_MAX_NEG = 65536  # draws of one edge in one epoch (csrc/umap.hip clamps alike)
+UMAP_INITS = ("spectral", "pca")
 
 
 # ---------------------------------------------------------------------------
@@ -338,6 +348,126 @@ class NumpyBackend:
     def tsne_p(self) -> np.ndarray:
         return self.P.copy()
 
+    # -- native UMAP --------------------------------------------------------------
+    # The arithmetic of csrc/umap.hip with fp64 distances and forces; the
+    # schedule state is float32 and advances by the same float32 operations as
+    # on the device, so both backends fire the same edges and draw the same
+    # negative samples.
+    def knn(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(d2 [N][k], idx int32 [N][k]): the k smallest squared distances of
+        every row, self included, ascending, a tie to the lower index.  O(N^2)."""
+        from scipy.spatial.distance import cdist
+
+        k = _check_k(k, self.n)
+        d2 = np.empty((self.n, k), dtype=np.float64)
+        idx = np.empty((self.n, k), dtype=np.int32)
+        for s, e in self._row_chunks(self.n):
+            full = cdist(self.X[s:e], self.X, "sqeuclidean")
+            kth = np.partition(full, k - 1, axis=1)[:, k - 1]
+            below = full <= kth[:, None]
+            exact = below.sum(axis=1) == k
+            rows = np.flatnonzero(exact)
+            if rows.size:
+                cols = np.nonzero(below[rows])[1].reshape(rows.size, k)  # ascending index
+                val = np.take_along_axis(full[rows], cols, axis=1)
+                order = np.argsort(val, axis=1, kind="stable")
+                d2[s + rows] = np.take_along_axis(val, order, axis=1)
+                idx[s + rows] = np.take_along_axis(cols, order, axis=1)
+            for r in np.flatnonzero(~exact):  # ties at the k-th distance: the lowest indices win
+                order = np.argsort(full[r], kind="stable")[:k]
+                d2[s + r] = full[r, order]
+                idx[s + r] = order
+        self.set_knn(d2, idx)
+        return d2.copy(), idx.copy()
+
+    def set_knn(self, d2: np.ndarray, idx: np.ndarray) -> None:
+        d2, idx = _check_knn(d2, idx, self.n)
+        self._knn_d2 = np.ascontiguousarray(d2, dtype=np.float64)
+        self._knn_idx = np.ascontiguousarray(idx, dtype=np.int32)
+
+    def knn_columns(self) -> int:
+        return 0 if getattr(self, "_knn_idx", None) is None else self._knn_idx.shape[1]
+
+    def knn_indices(self, k: int) -> np.ndarray:
+        return self._knn_idx[:, :k].copy()
+
+    def umap_fuzzy(self, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(rho [N], sigma [N], memberships [N][k]) of umap-learn's
+        ``smooth_knn_dist`` and ``compute_membership_strengths`` over the first
+        k columns of the kNN result, every row at once."""
+        k = _check_k(k, self.n)
+        if self.knn_columns() < k:
+            raise ValueError(f"ssip.analytics: umap_fuzzy({k}) needs a kNN result of at least {k} columns")
+        n = self.n
+        dist = np.sqrt(self._knn_d2[:, :k])
+        pos = dist > 0.0
+        rho = np.where(pos.any(axis=1), np.where(pos, dist, np.inf).min(axis=1), 0.0)
+        target = np.log2(float(k))
+        lo, hi, mid = np.zeros(n), np.full(n, np.inf), np.ones(n)
+        dd = dist - rho[:, None]
+        active = np.ones(n, dtype=bool)
+        for _ in range(64):
+            rows = np.flatnonzero(active)
+            if rows.size == 0:
+                break
+            d = dd[rows, 1:]
+            with np.errstate(over="ignore"):
+                psum = np.where(d > 0.0, np.exp(-np.where(d > 0.0, d, 0.0) / mid[rows, None]), 1.0).sum(axis=1)
+            done = np.abs(psum - target) < 1e-5
+            gt = (psum > target) & ~done
+            le = ~gt & ~done
+            r_gt, r_le = rows[gt], rows[le]
+            hi[r_gt] = mid[r_gt]
+            mid[r_gt] = (lo[r_gt] + hi[r_gt]) / 2.0
+            lo[r_le] = mid[r_le]
+            mid[r_le] = np.where(np.isinf(hi[r_le]), mid[r_le] * 2.0, (lo[r_le] + hi[r_le]) / 2.0)
+            active[rows[done]] = False
+        floor = 1e-3 * np.where(rho > 0.0, dist.mean(axis=1), dist.mean())
+        sigma = np.maximum(mid, floor)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            memb = np.where((dd <= 0.0) | (sigma[:, None] == 0.0), 1.0, np.exp(-np.maximum(dd, 0.0) / sigma[:, None]))
+        memb[self._knn_idx[:, :k] == np.arange(n)[:, None]] = 0.0
+        return rho, sigma, memb
+
+    def umap_begin(self, csr, y0: np.ndarray, a: float, b: float, seed: int, gamma: float = 1.0, state=None) -> None:
+        row_ptr, col, eps = _check_csr(csr, self.n)
+        self._u_rows = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(row_ptr))
+        self._u_col = col.astype(np.int64)
+        self._u_eps = eps
+        self._u_epn = eps / np.float32(UMAP_NEGATIVE_SAMPLE_RATE)
+        # both "next" arrays start at their period, or at a given (next_sample, next_neg)
+        self._u_next = np.array(self._u_eps if state is None else state[0], dtype=np.float32)
+        self._u_next_neg = np.array(self._u_epn if state is None else state[1], dtype=np.float32)
+        self._u_y = np.array(y0, dtype=np.float32).reshape(self.n, 2)
+        self._u_par = (float(np.float32(a)), float(np.float32(b)), float(np.float32(gamma)), int(seed) & 0xFFFFFFFF)
+
+    def umap_epoch(self, n: int, alpha: float) -> None:
+        a, b, gamma, seed = self._u_par
+        y = self._u_y.astype(np.float64)
+        nf = np.float32(n)
+        fire = np.flatnonzero(self._u_next <= nf)
+        force = np.zeros((self.n, 2))
+        if fire.size:
+            i, j = self._u_rows[fire], self._u_col[fire]
+            force += _scatter2(i, 2.0 * _umap_attraction(y[i] - y[j], a, b), self.n)
+            self._u_next[fire] = self._u_next[fire] + self._u_eps[fire]
+            epn = self._u_epn[fire]
+            n_neg = np.clip(((nf - self._u_next_neg[fire]) / epn).astype(np.int32), 0, UMAP_MAX_NEG)
+            self._u_next_neg[fire] = self._u_next_neg[fire] + n_neg.astype(np.float32) * epn
+            for p in range(int(n_neg.max())):
+                sel = n_neg > p
+                ei, vi = fire[sel], i[sel]
+                k = (umap_hash(seed, n, ei, p) % np.uint64(self.n)).astype(np.int64)
+                keep = k != vi
+                force += _scatter2(vi[keep], _umap_repulsion(y[vi[keep]] - y[k[keep]], a, b, gamma), self.n)
+        self._u_y = (y + float(np.float32(alpha)) * force).astype(np.float32)
+
+    def umap_embedding(self) -> np.ndarray:
+        return self._u_y.copy()
+
+    def umap_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self._u_next.copy(), self._u_next_neg.copy()
+
 
 class DeviceBackend:
     """libssip_hip.so backend (csrc/analytics.hip).  torch only owns the
@@ -501,6 +631,77 @@ class DeviceBackend:
 
     def tsne_p(self) -> np.ndarray:
         return self.P.cpu().numpy()
+
+    # -- native UMAP (csrc/umap.hip) -------------------------------------------
+    def knn(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        t = self._torch
+        k = _check_k(k, self.n)
+        self._knn_d2 = t.empty((self.n, k), dtype=t.float32, device=self.dev)
+        self._knn_idx = t.empty((self.n, k), dtype=t.int32, device=self.dev)
+        self._call("ssip_knn", self.n, self.d, k, self._p(self.X), self._p(self._knn_d2), self._p(self._knn_idx))
+        self._knn_idx_host = self._knn_idx.cpu().numpy()
+        return self._knn_d2.cpu().numpy(), self._knn_idx_host.copy()
+
+    def set_knn(self, d2: np.ndarray, idx: np.ndarray) -> None:
+        t = self._torch
+        d2, idx = _check_knn(d2, idx, self.n)
+        self._knn_idx_host = np.ascontiguousarray(idx, dtype=np.int32)
+        self._knn_d2 = t.from_numpy(np.ascontiguousarray(d2, dtype=np.float32)).to(self.dev)
+        self._knn_idx = t.from_numpy(self._knn_idx_host).to(self.dev)
+
+    def knn_columns(self) -> int:
+        return 0 if getattr(self, "_knn_idx", None) is None else int(self._knn_idx.shape[1])
+
+    def knn_indices(self, k: int) -> np.ndarray:
+        return self._knn_idx_host[:, :k].copy()
+
+    def umap_fuzzy(self, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        t = self._torch
+        k = _check_k(k, self.n)
+        if self.knn_columns() < k:
+            raise ValueError(f"ssip.analytics: umap_fuzzy({k}) needs a kNN result of at least {k} columns")
+        ws_bytes = int(self._lib.call("ssip_umap_workspace_bytes", self.n))
+        if ws_bytes < 0:
+            self._lib.check(ws_bytes, "ssip_umap_workspace_bytes")
+        ws = t.empty(ws_bytes, dtype=t.uint8, device=self.dev)
+        rho = t.empty(self.n, dtype=t.float32, device=self.dev)
+        sigma = t.empty(self.n, dtype=t.float32, device=self.dev)
+        memb = t.empty((self.n, k), dtype=t.float32, device=self.dev)
+        self._call("ssip_umap_fuzzy", self.n, k, self.knn_columns(), self._p(self._knn_d2), self._p(self._knn_idx),
+                   self._p(rho), self._p(sigma), self._p(memb), self._p(ws), ws_bytes)
+        return rho.cpu().numpy(), sigma.cpu().numpy(), memb.cpu().numpy()
+
+    def umap_begin(self, csr, y0: np.ndarray, a: float, b: float, seed: int, gamma: float = 1.0, state=None) -> None:
+        t = self._torch
+        row_ptr, col, eps = _check_csr(csr, self.n)
+
+        def up(arr, dtype):
+            return t.from_numpy(np.array(arr, dtype=dtype, order="C")).to(self.dev)  # a copy: the input may be read-only
+
+        self._u_row_ptr, self._u_col = up(row_ptr, np.int32), up(col, np.int32)
+        epn = eps / np.float32(UMAP_NEGATIVE_SAMPLE_RATE)
+        self._u_eps, self._u_epn = up(eps, np.float32), up(epn, np.float32)
+        # both "next" arrays start at their period, or at a given (next_sample, next_neg)
+        self._u_next = up(eps if state is None else state[0], np.float32)
+        self._u_next_neg = up(epn if state is None else state[1], np.float32)
+        if self._u_next.shape != self._u_eps.shape or self._u_next_neg.shape != self._u_eps.shape:
+            raise ValueError("ssip.analytics: the schedule state must hold one value per edge")
+        self._u_y = up(np.asarray(y0).reshape(self.n, 2), np.float32)
+        self._u_y2 = t.empty_like(self._u_y)
+        self._u_par = (float(a), float(b), float(gamma), int(seed) & 0xFFFFFFFF)
+
+    def umap_epoch(self, n: int, alpha: float) -> None:
+        a, b, gamma, seed = self._u_par
+        self._call("ssip_umap_epoch", self.n, self._p(self._u_row_ptr), self._p(self._u_col), self._p(self._u_eps),
+                   self._p(self._u_epn), self._p(self._u_next), self._p(self._u_next_neg), self._p(self._u_y),
+                   self._p(self._u_y2), a, b, gamma, float(alpha), int(n), seed)
+        self._u_y, self._u_y2 = self._u_y2, self._u_y
+
+    def umap_embedding(self) -> np.ndarray:
+        return self._u_y.cpu().numpy()
+
+    def umap_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self._u_next.cpu().numpy(), self._u_next_neg.cpu().numpy()
 
 
 def make_backend(X: np.ndarray, device: str = "cuda"):
@@ -681,3 +882,232 @@ def tsne_fit(X: np.ndarray, perplexity: float, seed: int = 42, max_iter: int = 1
                 break
         start = last + 1
     return backend.tsne_embedding().astype(np.float32), float(kl), last + 1
+
+
+# ---------------------------------------------------------------------------
+# native UMAP: host pieces shared by both backends
+# ---------------------------------------------------------------------------
+def _check_k(k: int, n: int) -> int:
+    k = int(k)
+    if not 2 <= k <= min(KNN_MAX_K, n):
+        raise ValueError(f"ssip.analytics: k = {k} outside 2..min({KNN_MAX_K}, N = {n})")
+    if n > UMAP_MAX_N:
+        raise ValueError(f"ssip.analytics: N = {n} above {UMAP_MAX_N}")
+    return k
+
+
+def _check_knn(d2, idx, n: int):
+    d2, idx = np.asarray(d2), np.asarray(idx)
+    if d2.shape != idx.shape or d2.ndim != 2 or d2.shape[0] != n or not 2 <= d2.shape[1] <= min(KNN_MAX_K, n):
+        raise ValueError(f"ssip.analytics: a kNN result is (d2 [N][k], idx [N][k]) with 2 <= k <= min({KNN_MAX_K}, N); "
+                         f"got {d2.shape} and {idx.shape} for N = {n}")
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise ValueError("ssip.analytics: kNN index outside 0..N-1")
+    return d2, idx
+
+
+def _check_csr(csr, n: int):
+    """(row_ptr int32 [N+1], col int32 [E], eps float32 [E]) of a layout graph,
+    validated before a kernel walks it."""
+    row_ptr, col, eps = (np.asarray(v) for v in csr)
+    row_ptr = row_ptr.astype(np.int64)
+    if row_ptr.shape != (n + 1,) or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0):
+        raise ValueError("ssip.analytics: row_ptr must be [N + 1], start at 0 and not decrease")
+    e = int(row_ptr[-1])
+    if col.shape != (e,) or eps.shape != (e,) or e >= 2 ** 31:
+        raise ValueError(f"ssip.analytics: col and eps must hold row_ptr[-1] = {e} edges")
+    if e and (col.min() < 0 or col.max() >= n):
+        raise ValueError("ssip.analytics: edge endpoint outside 0..N-1")
+    eps = eps.astype(np.float32)
+    if e and not (np.all(np.isfinite(eps)) and eps.min() >= 1.0):
+        raise ValueError("ssip.analytics: epochs_per_sample must be finite and >= 1 (it is max w / w)")
+    return row_ptr.astype(np.int32), col.astype(np.int32), eps
+
+
+def umap_hash(seed, n, e, p) -> np.ndarray:
+    """ssip_umap_hash of include/ssip.h with numpy integers (uint64 holding 32-bit values)."""
+    m32 = np.uint64(0xFFFFFFFF)
+
+    def u(v):
+        return np.asarray(v).astype(np.uint64) & m32
+
+    def mix(x):
+        x = x ^ (x >> np.uint64(16))
+        x = (x * np.uint64(0x7FEB352D)) & m32
+        x = x ^ (x >> np.uint64(15))
+        x = (x * np.uint64(0x846CA68B)) & m32
+        return x ^ (x >> np.uint64(16))
+
+    h = mix(((u(seed) * np.uint64(0x9E3779B1)) + u(n)) & m32)
+    h = mix(h ^ u(e))
+    return mix((h + ((u(p) * np.uint64(0x85EBCA77)) & m32)) & m32)
+
+
+def _scatter2(rows: np.ndarray, vals: np.ndarray, n: int) -> np.ndarray:
+    return np.stack([np.bincount(rows, weights=vals[:, c], minlength=n) for c in range(2)], axis=1)
+
+
+def _umap_attraction(diff: np.ndarray, a: float, b: float) -> np.ndarray:
+    d2 = (diff * diff).sum(axis=1)
+    ok = d2 > 0.0
+    safe = np.where(ok, d2, 1.0)
+    c = np.where(ok, -2.0 * a * b * safe ** (b - 1.0) / (a * safe ** b + 1.0), 0.0)
+    return np.clip(c[:, None] * diff, -4.0, 4.0)
+
+
+def _umap_repulsion(diff: np.ndarray, a: float, b: float, gamma: float) -> np.ndarray:
+    d2 = (diff * diff).sum(axis=1)
+    ok = d2 > 0.0
+    safe = np.where(ok, d2, 1.0)
+    c = np.where(ok, 2.0 * gamma * b / ((0.001 + safe) * (a * safe ** b + 1.0)), 0.0)
+    return np.clip(c[:, None] * diff, -4.0, 4.0)
+
+
+def umap_graph(idx: np.ndarray, memb: np.ndarray):
+    """W = A + A^T - A o A^T (scipy CSR, float32, sorted indices, no stored
+    zeros) of the directed memberships A[i][idx[i][c]] = memb[i][c].  Both
+    directions of an edge hold the same bits: the sum and the product commute."""
+    from scipy.sparse import csr_matrix
+
+    n, k = idx.shape
+    rows = np.repeat(np.arange(n, dtype=np.int64), k)
+    A = csr_matrix((np.asarray(memb, dtype=np.float32).ravel(), (rows, np.asarray(idx, dtype=np.int64).ravel())),
+                   shape=(n, n))
+    A.eliminate_zeros()
+    T = A.T.tocsr()
+    W = (A + T - A.multiply(T)).tocsr().astype(np.float32)
+    W.eliminate_zeros()
+    W.sort_indices()
+    return W
+
+
+def find_ab_params(spread: float, min_dist: float) -> Tuple[float, float]:
+    """umap-learn's find_ab_params: fit 1 / (1 + a x^(2b)) to the offset exponential."""
+    from scipy.optimize import curve_fit
+
+    def curve(x, a, b):
+        return 1.0 / (1.0 + a * x ** (2 * b))
+
+    xv = np.linspace(0, spread * 3, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    params, _ = curve_fit(curve, xv, yv)
+    return float(params[0]), float(params[1])
+
+
+def umap_schedule(W, n_epochs: int):
+    """(row_ptr int32, col int32, epochs_per_sample float32) of the edges with
+    w >= max w / n_epochs; epochs_per_sample = max w / w in float32."""
+    W = W.tocsr()
+    w = W.data.astype(np.float32)
+    if w.size == 0:
+        raise ValueError("ssip.analytics: the UMAP graph has no edges")
+    wmax = np.float32(w.max())
+    keep = ~(w < wmax / np.float32(n_epochs))
+    rows = np.repeat(np.arange(W.shape[0]), np.diff(W.indptr))[keep]
+    row_ptr = np.zeros(W.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=W.shape[0]), out=row_ptr[1:])
+    return row_ptr.astype(np.int32), W.indices[keep].astype(np.int32), (wmax / w[keep]).astype(np.float32)
+
+
+def _fix_signs(v: np.ndarray) -> np.ndarray:
+    """Each column's largest-magnitude entry made positive."""
+    big = v[np.abs(v).argmax(axis=0), np.arange(v.shape[1])]
+    return v * np.where(big < 0.0, -1.0, 1.0)
+
+
+def _pca_layout(X: np.ndarray) -> np.ndarray:
+    Xc = np.asarray(X, dtype=np.float64)
+    Xc = Xc - Xc.mean(axis=0)
+    U, S, _ = np.linalg.svd(Xc, full_matrices=False)
+    y = np.zeros((Xc.shape[0], 2))
+    m = min(2, S.size)
+    y[:, :m] = _fix_signs(U[:, :m] * S[:m])
+    return y
+
+
+def _spectral_layout(W) -> Optional[np.ndarray]:
+    """The two non-trivial bottom eigenvectors of the symmetric normalised
+    Laplacian, or None when the graph is not connected or ARPACK gives up."""
+    from scipy.sparse import diags, identity
+    from scipy.sparse.csgraph import connected_components
+    from scipy.sparse.linalg import ArpackError, eigsh
+
+    n = W.shape[0]
+    k = 3
+    ncv = max(2 * k + 1, int(np.sqrt(n)))
+    if n <= ncv or connected_components(W, directed=False)[0] > 1:
+        return None
+    W64 = W.astype(np.float64)
+    deg = np.asarray(W64.sum(axis=1)).ravel()
+    D = diags(1.0 / np.sqrt(deg))
+    L = identity(n, dtype=np.float64) - D @ W64 @ D
+    try:
+        vals, vecs = eigsh(L, k, which="SM", ncv=ncv, tol=1e-4, v0=np.ones(n), maxiter=n * 5)
+    except ArpackError:  # ArpackNoConvergence is one
+        return None
+    return _fix_signs(vecs[:, np.argsort(vals)[1:3]])
+
+
+def umap_init(X: np.ndarray, W, init: str, seed: int) -> Tuple[np.ndarray, str]:
+    """(y0 float32 [N][2], the init that was used)."""
+    if init not in UMAP_INITS:
+        raise ValueError("ssip.analytics: UMAP init must be one of: " + ", ".join(UMAP_INITS))
+    y, used = None, init
+    if init == "spectral":
+        y = _spectral_layout(W)
+        if y is None:
+            logging.getLogger(__name__).warning(
+                "UMAP spectral init: the graph is not connected or ARPACK did not converge; using the PCA init")
+            used = "pca"
+    if y is None:
+        y = _pca_layout(X)
+    y = y + np.random.RandomState(seed).normal(scale=1e-4, size=y.shape)
+    lo, span = y.min(axis=0), y.max(axis=0) - y.min(axis=0)
+    return (10.0 * (y - lo) / np.where(span > 0.0, span, 1.0)).astype(np.float32), used
+
+
+def knn_graph(X: np.ndarray, k: int, device: str = "cuda", backend=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(d2 [N][k], idx int32 [N][k]): exact k nearest neighbours of every row,
+    self included, ascending, a tie to the lower index.  2 <= k <= min(64, N)."""
+    backend = backend if backend is not None else make_backend(X, device)
+    return backend.knn(int(k))
+
+
+def umap_fit(X: np.ndarray, n_neighbors: int, min_dist: float, seed: int = 42, n_epochs: Optional[int] = None,
+             init: str = "spectral", device: str = "cuda", backend=None, knn=None):
+    """(embedding float32 [N][2], info) of umap-learn's algorithm under the
+    defaults of ``umap.UMAP(n_components=2, metric="euclidean")``: exact kNN,
+    ``smooth_knn_dist`` and the membership strengths on the backend; the fuzzy
+    union, ``find_ab_params``, the edge schedule and the spectral / PCA init on
+    the host; then ``n_epochs`` (500 up to 10,000 points, else 200) layout
+    epochs on the backend with alpha = 1 - n / n_epochs and no read-back.
+
+    Epochs are Jacobi-ordered and the negative samples come from a
+    counter-based hash, so an embedding is reproducible bit for bit but is not
+    comparable point for point with umap-learn's (sequential updates, its own
+    RNG).  ``knn`` = a precomputed ``(d2, idx)`` of at least ``n_neighbors``
+    columns; a backend that already holds one (``backend.knn``) is reused.
+    ``info``: a, b, n_epochs, n_edges (directed, after pruning), init."""
+    X = np.asarray(X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    n = X.shape[0]
+    k = _check_k(n_neighbors, n)
+    backend = backend if backend is not None else make_backend(X, device)
+    if knn is not None:
+        backend.set_knn(*knn)
+    if backend.knn_columns() < k:
+        backend.knn(k)
+    _, _, memb = backend.umap_fuzzy(k)
+    W = umap_graph(backend.knn_indices(k), memb)
+    a, b = find_ab_params(1.0, float(min_dist))
+    n_epochs = int(n_epochs) if n_epochs is not None else (500 if n <= 10000 else 200)
+    if n_epochs < 1:
+        raise ValueError(f"ssip.analytics: n_epochs = {n_epochs} must be >= 1")
+    csr = umap_schedule(W, n_epochs)
+    y0, used = umap_init(X, W, init, int(seed))
+    backend.umap_begin(csr, y0, a, b, int(seed))
+    for ep in range(n_epochs):
+        backend.umap_epoch(ep, 1.0 - ep / n_epochs)
+    info = {"a": a, "b": b, "n_epochs": n_epochs, "n_edges": int(csr[1].shape[0]), "init": used}
+    return backend.umap_embedding().astype(np.float32), info
