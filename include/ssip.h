@@ -419,7 +419,8 @@ int ssip_kmeans_assign(int64_t N, int d, int K, const float* X, const float* cen
  * workgroup order: new_centres[k] = mean of the points assigned to k,
  * counts[k] = their number; an empty cluster keeps centres[k] and reports
  * counts[k] = 0.  scalars (4 fp64): {sum |new_centres - centres|^2, inertia =
- * sum mind2, number of changed labels, number of empty clusters}. */
+ * sum mind2, number of changed labels, number of empty clusters}.  The
+ * workspace is the one ssip_kmeans_assign filled (16-byte aligned). */
 int ssip_kmeans_update(int64_t N, int d, int K, const void* workspace, int64_t workspace_bytes, const float* centres,
                        float* new_centres, int32_t* counts, double* scalars, void* stream);
 /* X against itself under d2 <= eps^2: degree[i] = number of such j (self
@@ -493,7 +494,10 @@ int ssip_tsne_update(int N, void* workspace, int64_t workspace_bytes, float* Y, 
  * row i of X (fp32 [N][d], 1 <= d <= 512; direct difference, feature order, as
  * the analytics section) to any row, self included, ascending, with their
  * column indices; equal distances are ordered by index.  2 <= k <= min(64, N).
- * The first k' columns of a k result are the k' result bit for bit. */
+ * The first k' columns of a k result are the k' result bit for bit.  A
+ * pairwise kernel of the analytics section: the column walk and the selection
+ * are those of ssip_pairwise_kth with the column index in the key, so
+ * sqrtf(d2[i][k - 1]) == kth[i] of ssip_pairwise_kth(k) bit for bit. */
 int ssip_knn(int N, int d, int k, const float* X, float* d2, int32_t* idx, void* stream);
 /* bytes of the workspace of ssip_umap_fuzzy: per-row distance sums (fp64 [N])
  * and their total */

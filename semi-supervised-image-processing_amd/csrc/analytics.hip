@@ -3,7 +3,9 @@
 // and the per-cluster distance sums behind the silhouette score.  These stand
 // in for the sklearn calls the reference makes at src/clustering.py:330-438
 // (KMeans.fit_predict, DBSCAN.fit_predict, silhouette_score,
-// NearestNeighbors.kneighbors).
+// NearestNeighbors.kneighbors).  The exact k nearest neighbours that the
+// native UMAP (umap.hip) starts from are a pairwise primitive too and live
+// here (ssip_knn).
 //
 // Points are fp32, row-major [N][d], 1 <= d <= 512.
 //
@@ -19,9 +21,11 @@
 //
 // No atomics; every reduction runs in a fixed order, so all outputs are
 // bit-reproducible from run to run.  Two thread layouts:
-//   A (eps graph, k-th distance): a workgroup owns RA = 64 rows and walks all
-//     columns in tiles of 64; lane = column, each wave holds 16 rows, so one
-//     wave ballot is 64 columns of one row = two bitmap words.
+//   A (eps graph, k-th distance, exact kNN; the t-SNE distances of tsne.hip):
+//     a workgroup owns RA = 64 rows and walks all columns in tiles of 64
+//     (pairwise_tile.h); lane = column, each wave holds 16 rows, so one wave
+//     ballot is 64 columns of one row = two bitmap words.  The k-th distance
+//     and the kNN are one selection body over two key types.
 //   B (assign, cluster sums): a workgroup owns RB = 256 rows, thread = row,
 //     and walks the columns (centres / points in label order) in tiles of 16;
 //     everything that depends on the column is uniform across the workgroup.
@@ -37,109 +41,76 @@ constexpr int CT = 16;        // layout B: columns per tile
 constexpr int KMAX = 64;      // centres
 constexpr int UPD_NT = 1024;  // update: one workgroup
 
-// ascending bitonic sort of one value per lane across the wave
-__device__ __forceinline__ float wave_sort(float v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const float p = __shfl_xor(v, j, 64);
-      const bool up = (lane & k) == 0;
-      const bool lo = (lane & j) == 0;
-      v = (lo == up) ? fminf(v, p) : fmaxf(v, p);
-    }
-  }
-  return v;
-}
-// best: ascending 64 smallest so far; cand: 64 new values.  Returns the
-// ascending 64 smallest of the union.
-__device__ __forceinline__ float wave_merge_smallest(float best, float cand, int lane) {
-  const float s = wave_sort(cand, lane);
-  float m = fminf(best, __shfl(s, 63 - lane, 64));  // bitonic, holds the 64 smallest
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const float p = __shfl_xor(m, j, 64);
-    m = (lane & j) == 0 ? fminf(m, p) : fmaxf(m, p);
-  }
-  return m;
-}
+constexpr int KNN_MAX_N = 1 << 20;
+constexpr int KNN_MAX_K = 64;
 
-// MODE 0: degree + adjacency bitmap of d2 <= eps2.  MODE 1: k-th smallest distance.
-template <int MODE>
-__global__ __launch_bounds__(NT) void pairwise_a_kernel(int N, int d, const float* __restrict__ X, float eps2, int kk,
-                                                        int* __restrict__ degree, uint32_t* __restrict__ bitmap,
-                                                        float* __restrict__ kth) {
-  __shared__ __attribute__((aligned(16))) float xr[DC * XR_LD];
-  __shared__ float xc[64 * XC_LD];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+// ---------------------------------------------------------------------------
+// layout A (the walk and the selection are pairwise_tile.h's)
+// ---------------------------------------------------------------------------
+// degree + adjacency bitmap of d2 <= eps2
+__global__ __launch_bounds__(NT) void pairwise_eps_kernel(int N, int d, const float* __restrict__ X, float eps2,
+                                                          int* __restrict__ degree, uint32_t* __restrict__ bitmap) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row0 = blockIdx.x * RA;
-  const int nch = (d + DC - 1) / DC, ntile = (N + 63) / 64;
   const int W = (N + 31) / 32;
-
-  float best[16];
   int deg[16];
 #pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    best[u] = INFINITY;
-    deg[u] = 0;
-  }
-
-  float pre_r[TQ], pre_c[TQ];
-  fetch_tile_a(pre_r, X, row0, N, d, 0, tid);
-  fetch_tile_a(pre_c, X, 0, N, d, 0, tid);
-  float acc[16];
-  const int steps = ntile * nch;
-  for (int it = 0; it < steps; ++it) {
-    const int jt = it / nch, ch = it - jt * nch;
-    // a single-chunk row tile stays resident for the whole column walk
-    if (nch > 1 || it == 0) put_rows_a(xr, pre_r, tid);
-    put_cols_a(xc, pre_c, tid);
-    __syncthreads();
-    if (it + 1 < steps) {  // next step's tiles, in flight during the arithmetic below
-      const int jn = (it + 1) / nch, cn = (it + 1) - jn * nch;
-      if (nch > 1) fetch_tile_a(pre_r, X, row0, N, d, cn * DC, tid);
-      fetch_tile_a(pre_c, X, jn * 64, N, d, cn * DC, tid);
-    }
-    if (ch == 0) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc[u] = 0.f;
-    }
-    accumulate_a(acc, xr, xc, w, lane);
-    __syncthreads();
-    if (ch != nch - 1) continue;
+  for (int u = 0; u < 16; ++u) deg[u] = 0;
+  walk_columns_a(N, d, X, row0, [&](int jt, const float(&acc)[16]) {
     const int j = jt * 64 + lane;
-    if (MODE == 0) {
-      unsigned long long mine = 0;
+    unsigned long long mine = 0;
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int i = row0 + w * 16 + u;
-        const unsigned long long m = __ballot(j < N && i < N && acc[u] <= eps2);
-        deg[u] += __popcll(m);
-        if ((lane >> 1) == u) mine = m;
-      }
-      // lanes 0..31 store the wave's 16 rows x 2 words
-      const int i = row0 + w * 16 + (lane >> 1), wi = jt * 2 + (lane & 1);
-      if (lane < 32 && i < N && wi < W)
-        bitmap[(long)i * W + wi] = (uint32_t)((lane & 1) ? (mine >> 32) : (mine & 0xffffffffull));
-    } else {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float cand = j < N ? acc[u] : INFINITY;
-        const float thr = __shfl(best[u], kk - 1, 64);
-        if (__any(cand < thr)) best[u] = wave_merge_smallest(best[u], cand, lane);  // wave-uniform branch
-      }
+    for (int u = 0; u < 16; ++u) {
+      const int i = row0 + w * 16 + u;
+      const unsigned long long m = __ballot(j < N && i < N && acc[u] <= eps2);
+      deg[u] += __popcll(m);
+      if ((lane >> 1) == u) mine = m;
     }
-  }
+    // lanes 0..31 store the wave's 16 rows x 2 words
+    const int i = row0 + w * 16 + (lane >> 1), wi = jt * 2 + (lane & 1);
+    if (lane < 32 && i < N && wi < W)
+      bitmap[(long)i * W + wi] = (uint32_t)((lane & 1) ? (mine >> 32) : (mine & 0xffffffffull));
+  });
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
     const int i = row0 + w * 16 + u;
-    if (MODE == 0) {
-      if (lane == u && i < N) degree[i] = deg[u];
-    } else {
-      const float v = __shfl(best[u], kk - 1, 64);
-      if (lane == u && i < N) kth[i] = sqrtf(v);
-    }
+    if (lane == u && i < N) degree[i] = deg[u];
   }
+}
+
+// k-th distance: the key is the squared distance alone
+struct DistKey {
+  typedef float T;
+  static __device__ T worst() { return INFINITY; }
+  static __device__ T make(float d2, int) { return d2; }
+};
+// kNN: the bits of the squared distance above the column index.  d2 >= 0, so
+// keys order by distance and then by index, and no two keys are equal; hence
+// the first k' keys of a k result are the k' result.
+struct DistIndexKey {
+  typedef u64 T;
+  static __device__ T worst() { return ~0ull; }
+  static __device__ T make(float d2, int j) { return ((u64)__float_as_uint(d2) << 32) | (u64)(uint32_t)j; }
+};
+
+__global__ __launch_bounds__(NT) void pairwise_kth_kernel(int N, int d, int kk, const float* __restrict__ X,
+                                                          float* __restrict__ kth) {
+  const int lane = threadIdx.x & 63;
+  select_smallest_a<DistKey>(N, d, kk, X, [&](int i, float key) {
+    if (lane == kk - 1) kth[i] = sqrtf(key);
+  });
+}
+
+// k <= N, so the first k keys of every row are real candidates
+__global__ __launch_bounds__(NT) void knn_kernel(int N, int d, int kk, const float* __restrict__ X,
+                                                 float* __restrict__ d2out, int32_t* __restrict__ idxout) {
+  const int lane = threadIdx.x & 63;
+  select_smallest_a<DistIndexKey>(N, d, kk, X, [&](int i, u64 key) {
+    if (lane < kk) {
+      d2out[(long)i * kk + lane] = __uint_as_float((uint32_t)(key >> 32));
+      idxout[(long)i * kk + lane] = (int32_t)(uint32_t)(key & 0xffffffffull);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -438,13 +409,6 @@ __global__ __launch_bounds__(NT) void cluster_sums_kernel(int N, int d, int K, c
   if (cur >= 0 && row < N) sums[row * K + cur] = run;
 }
 
-int check_points(const char* what, long N, int d, const void* X) {
-  SSIP_REQUIRE(N >= 1, SSIP_ERR_ARG, "%s: N = %ld must be >= 1", what, N);
-  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "%s: d = %d outside 1..512", what, d);
-  SSIP_REQUIRE(X != nullptr, SSIP_ERR_ARG, "%s: null point matrix", what);
-  return SSIP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -461,11 +425,7 @@ int ssip_kmeans_assign(int64_t N, int d, int K, const float* X, const float* cen
   if (int rc = check_points("ssip_kmeans_assign", N, d, X)) return rc;
   SSIP_REQUIRE(K >= 2 && K <= KMAX, SSIP_ERR_ARG, "ssip_kmeans_assign: K = %d outside 2..64", K);
   SSIP_REQUIRE(centres && labels && mind2 && workspace, SSIP_ERR_ARG, "ssip_kmeans_assign: null pointer");
-  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
-               "ssip_kmeans_assign: workspace must be 16-byte aligned");
-  SSIP_REQUIRE(workspace_bytes >= kmeans_ws_bytes(N, d, K), SSIP_ERR_WORKSPACE,
-               "ssip_kmeans_assign: workspace of %ld bytes, need %ld", (long)workspace_bytes,
-               kmeans_ws_bytes(N, d, K));
+  if (int rc = check_workspace("ssip_kmeans_assign", workspace, workspace_bytes, kmeans_ws_bytes(N, d, K))) return rc;
   const long G = kmeans_groups(N);
   SSIP_REQUIRE(G <= 0x7fffffffL, SSIP_ERR_ARG, "ssip_kmeans_assign: N = %ld too large", (long)N);
   SSIP_KLAUNCH(kmeans_assign_kernel, dim3((unsigned)G), dim3(NT), 0, (hipStream_t)stream, (long)N, d, K, X, centres,
@@ -479,9 +439,8 @@ int ssip_kmeans_update(int64_t N, int d, int K, const void* workspace, int64_t w
                "ssip_kmeans_update: need N >= 1, 1 <= d <= 512, 2 <= K <= 64 (N=%ld d=%d K=%d)", (long)N, d, K);
   SSIP_REQUIRE(workspace && centres && new_centres && counts && scalars, SSIP_ERR_ARG,
                "ssip_kmeans_update: null pointer");
-  SSIP_REQUIRE(workspace_bytes >= kmeans_ws_bytes(N, d, K), SSIP_ERR_WORKSPACE,
-               "ssip_kmeans_update: workspace of %ld bytes, need %ld", (long)workspace_bytes,
-               kmeans_ws_bytes(N, d, K));
+  // the alignment is the one ssip_kmeans_assign demands of the same buffer
+  if (int rc = check_workspace("ssip_kmeans_update", workspace, workspace_bytes, kmeans_ws_bytes(N, d, K))) return rc;
   SSIP_KLAUNCH(kmeans_update_kernel, dim3(1), dim3(UPD_NT), 0, (hipStream_t)stream, kmeans_groups(N), d, K,
                kmeans_ws(const_cast<void*>(workspace), N, d, K), centres, new_centres, counts, scalars);
   return ssip::check_launch("ssip_kmeans_update");
@@ -493,8 +452,8 @@ int ssip_pairwise_eps(int N, int d, const float* X, float eps, int32_t* degree, 
                "ssip_pairwise_eps: N = %d above 65536 (the adjacency bitmap would exceed 512 MB)", N);
   SSIP_REQUIRE(eps >= 0.f, SSIP_ERR_ARG, "ssip_pairwise_eps: eps = %g must be >= 0", (double)eps);
   SSIP_REQUIRE(degree && bitmap, SSIP_ERR_ARG, "ssip_pairwise_eps: null pointer");
-  SSIP_KLAUNCH(pairwise_a_kernel<0>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps, 1,
-               degree, bitmap, (float*)nullptr);
+  SSIP_KLAUNCH(pairwise_eps_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps,
+               degree, bitmap);
   return ssip::check_launch("ssip_pairwise_eps");
 }
 
@@ -503,9 +462,18 @@ int ssip_pairwise_kth(int N, int d, int k, const float* X, float* kth, void* str
   SSIP_REQUIRE(k >= 1 && k <= 64, SSIP_ERR_ARG, "ssip_pairwise_kth: k = %d outside 1..64", k);
   SSIP_REQUIRE(k <= N, SSIP_ERR_ARG, "ssip_pairwise_kth: k = %d neighbours asked of N = %d points", k, N);
   SSIP_REQUIRE(kth != nullptr, SSIP_ERR_ARG, "ssip_pairwise_kth: null pointer");
-  SSIP_KLAUNCH(pairwise_a_kernel<1>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, 0.f, k,
-               (int*)nullptr, (uint32_t*)nullptr, kth);
+  SSIP_KLAUNCH(pairwise_kth_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, k, X, kth);
   return ssip::check_launch("ssip_pairwise_kth");
+}
+
+int ssip_knn(int N, int d, int k, const float* X, float* d2, int32_t* idx, void* stream) {
+  SSIP_REQUIRE(N >= 2 && N <= KNN_MAX_N, SSIP_ERR_ARG, "ssip_knn: N = %d outside 2..%d", N, KNN_MAX_N);
+  if (int rc = check_points("ssip_knn", N, d, X)) return rc;
+  SSIP_REQUIRE(k >= 2 && k <= KNN_MAX_K, SSIP_ERR_ARG, "ssip_knn: k = %d outside 2..%d", k, KNN_MAX_K);
+  SSIP_REQUIRE(k <= N, SSIP_ERR_ARG, "ssip_knn: k = %d neighbours asked of N = %d points", k, N);
+  SSIP_REQUIRE(d2 && idx, SSIP_ERR_ARG, "ssip_knn: null pointer");
+  SSIP_KLAUNCH(knn_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, k, X, d2, idx);
+  return ssip::check_launch("ssip_knn");
 }
 
 int ssip_pairwise_cluster_sums(int N, int d, int K, const float* X, const int32_t* labels, const int32_t* order,

@@ -49,6 +49,22 @@ int check_launch(const char* what);
     }                                        \
   } while (0)
 
+// argument checks shared by the analytics entry points (analytics.hip, tsne.hip, umap.hip)
+inline int check_points(const char* what, long N, int d, const void* X) {
+  SSIP_REQUIRE(N >= 1, SSIP_ERR_ARG, "%s: N = %ld must be >= 1", what, N);
+  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "%s: d = %d outside 1..512", what, d);
+  SSIP_REQUIRE(X != nullptr, SSIP_ERR_ARG, "%s: null point matrix", what);
+  return SSIP_OK;
+}
+// a caller-provided workspace: present, 16-byte aligned, at least `need` bytes
+inline int check_workspace(const char* what, const void* workspace, long bytes, long need) {
+  SSIP_REQUIRE(workspace != nullptr, SSIP_ERR_ARG, "%s: null workspace", what);
+  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
+               "%s: workspace must be 16-byte aligned", what);
+  SSIP_REQUIRE(bytes >= need, SSIP_ERR_WORKSPACE, "%s: workspace of %ld bytes, need %ld", what, bytes, need);
+  return SSIP_OK;
+}
+
 // ---------------------------------------------------------------------------
 // scalar conversions
 // ---------------------------------------------------------------------------
@@ -118,6 +134,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// sum over a workgroup of 256 threads, the same value in every thread: wave
+// butterfly, then the four waves in index order.  `slot` holds 4 doubles and
+// must not be reused before the next barrier of the caller.
+__device__ __forceinline__ double block_sum_d(double v, double* slot, int tid) {
+  v = wave_sum_d(v);
+  if ((tid & 63) == 0) slot[tid >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < 256 / 64; ++q) s += slot[q];
+  return s;
 }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }

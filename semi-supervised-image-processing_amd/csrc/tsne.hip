@@ -88,59 +88,21 @@ inline TsneWs tsne_ws(void* base, long N) {
   return ws;
 }
 
-// sum over the workgroup's NT threads, the same value in every thread: wave
-// butterfly, then the waves in order.  `slot` holds NT / 64 doubles and must
-// not be reused before the next barrier of the caller.
-__device__ __forceinline__ double block_sum_d(double v, double* slot, int tid) {
-  v = wave_sum_d(v);
-  if ((tid & 63) == 0) slot[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int q = 0; q < NT / 64; ++q) s += slot[q];
-  return s;
-}
-
 // ---------------------------------------------------------------------------
 // conditional P
 // ---------------------------------------------------------------------------
-// P[i][j] = |x_i - x_j|^2, the walk of pairwise_a_kernel (analytics.hip)
+// P[i][j] = |x_i - x_j|^2
 __global__ __launch_bounds__(NT) void tsne_d2_kernel(int N, int d, const float* __restrict__ X, float* __restrict__ P) {
-  __shared__ __attribute__((aligned(16))) float xr[DC * XR_LD];
-  __shared__ float xc[64 * XC_LD];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row0 = blockIdx.x * RA;
-  const int nch = (d + DC - 1) / DC, ntile = (N + 63) / 64;
-
-  float pre_r[TQ], pre_c[TQ];
-  fetch_tile_a(pre_r, X, row0, N, d, 0, tid);
-  fetch_tile_a(pre_c, X, 0, N, d, 0, tid);
-  float acc[16];
-  const int steps = ntile * nch;
-  for (int it = 0; it < steps; ++it) {
-    const int jt = it / nch, ch = it - jt * nch;
-    if (nch > 1 || it == 0) put_rows_a(xr, pre_r, tid);
-    put_cols_a(xc, pre_c, tid);
-    __syncthreads();
-    if (it + 1 < steps) {
-      const int jn = (it + 1) / nch, cn = (it + 1) - jn * nch;
-      if (nch > 1) fetch_tile_a(pre_r, X, row0, N, d, cn * DC, tid);
-      fetch_tile_a(pre_c, X, jn * 64, N, d, cn * DC, tid);
-    }
-    if (ch == 0) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc[u] = 0.f;
-    }
-    accumulate_a(acc, xr, xc, w, lane);
-    __syncthreads();
-    if (ch != nch - 1) continue;
+  walk_columns_a(N, d, X, row0, [&](int jt, const float(&acc)[16]) {
     const int j = jt * 64 + lane;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int i = row0 + w * 16 + u;
       if (i < N && j < N) P[(long)i * N + j] = acc[u];
     }
-  }
+  });
 }
 
 // One workgroup per row: sklearn's _binary_search_perplexity over the row of
@@ -438,12 +400,7 @@ __global__ __launch_bounds__(FIN_NT) void tsne_finish_kernel(int G, TsneWs ws, d
 int check_tsne(const char* what, long N, const void* workspace, long workspace_bytes) {
   SSIP_REQUIRE(N >= 2 && N <= TSNE_MAX_N, SSIP_ERR_ARG, "%s: N = %ld outside 2..%d (P is N^2 floats)", what, N,
                TSNE_MAX_N);
-  SSIP_REQUIRE(workspace != nullptr, SSIP_ERR_ARG, "%s: null workspace", what);
-  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
-               "%s: workspace must be 16-byte aligned", what);
-  SSIP_REQUIRE(workspace_bytes >= tsne_ws_bytes(N), SSIP_ERR_WORKSPACE, "%s: workspace of %ld bytes, need %ld", what,
-               workspace_bytes, tsne_ws_bytes(N));
-  return SSIP_OK;
+  return check_workspace(what, workspace, workspace_bytes, tsne_ws_bytes(N));
 }
 
 }  // namespace
@@ -458,9 +415,9 @@ int64_t ssip_tsne_workspace_bytes(int64_t N) {
 
 int ssip_tsne_cond_p(int N, int d, const float* X, float perplexity, float* P, double* beta, void* stream) {
   SSIP_REQUIRE(N >= 2 && N <= TSNE_MAX_N, SSIP_ERR_ARG, "ssip_tsne_cond_p: N = %d outside 2..%d", N, TSNE_MAX_N);
-  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "ssip_tsne_cond_p: d = %d outside 1..512", d);
+  if (int rc = check_points("ssip_tsne_cond_p", N, d, X)) return rc;
   SSIP_REQUIRE(perplexity > 0.f, SSIP_ERR_ARG, "ssip_tsne_cond_p: perplexity = %g must be > 0", (double)perplexity);
-  SSIP_REQUIRE(X && P && beta, SSIP_ERR_ARG, "ssip_tsne_cond_p: null pointer");
+  SSIP_REQUIRE(P && beta, SSIP_ERR_ARG, "ssip_tsne_cond_p: null pointer");
   SSIP_KLAUNCH(tsne_d2_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, P);
   SSIP_KLAUNCH(tsne_bisect_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, N, log((double)perplexity), P, beta);
   return ssip::check_launch("ssip_tsne_cond_p");

@@ -1,5 +1,6 @@
 // Native UMAP (reference src/clustering.py:279-306, which calls umap.UMAP):
-// the three device stages of ssip.analytics.umap_fit.  The algorithm is
+// the two device stages of ssip.analytics.umap_fit that follow the exact kNN
+// (ssip_knn, a pairwise kernel of analytics.hip).  The algorithm is
 // umap-learn's (nearest neighbours -> smooth_knn_dist -> membership strengths
 // -> optimize_layout_euclidean); the graph symmetrisation, the a / b curve
 // fit, the schedule and the initial layout are O(N k) host work.
@@ -7,13 +8,6 @@
 // Everything is fp32 unless said otherwise.  No atomics; every reduction runs
 // in a fixed order, so all outputs are bit-reproducible from run to run.
 //
-//   knn:    layout A of analytics.hip (pairwise_tile.h), the walk of
-//           pairwise_a_kernel<1>.  A candidate is one 64-bit key, the bits of
-//           the squared distance above the column index: d2 >= 0, so keys order
-//           by distance and then by index, and no two keys are equal.  Each of
-//           a wave's 16 rows keeps its 64 smallest keys ascending, one per
-//           lane; a column tile is merged in (bitonic sort + bitonic merge)
-//           only when one of its keys is below the row's current k-th key.
 //   fuzzy:  one wave per row, lane = neighbour column.  rho by a wave minimum,
 //           sigma by umap's bisection with exp and the sums in fp64.  The mean
 //           of all distances (the sigma floor of rows with rho = 0) is reduced
@@ -26,103 +20,17 @@
 //           running sums through a fixed butterfly) are fp64, then one plain
 //           8-byte store of the fp32 position.
 #include "ssip_common.h"
-#include "pairwise_tile.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int UMAP_MAX_N = 1 << 20;
-constexpr int KNN_MAX_K = 64;
+constexpr int KNN_MAX_K = 64;       // columns of a kNN result (ssip_knn)
+constexpr int NT = 256;             // threads per workgroup: four rows / vertices, one per wave
 constexpr int FIN_NT = 256;         // global mean: one workgroup
 constexpr int BISECT_STEPS = 64;    // umap's n_iter
 constexpr int MAX_NEG = 65536;      // draws of one edge in one epoch (eps >= 1 gives n_neg <= 5 n)
-typedef unsigned long long u64;
-
-// ---------------------------------------------------------------------------
-// exact kNN
-// ---------------------------------------------------------------------------
-// ascending bitonic sort of one key per lane across the wave
-__device__ __forceinline__ u64 wave_sort_key(u64 v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const u64 p = __shfl_xor(v, j, 64);
-      const bool up = (lane & k) == 0;
-      const bool lo = (lane & j) == 0;
-      v = (lo == up) ? (p < v ? p : v) : (p > v ? p : v);
-    }
-  }
-  return v;
-}
-// best: ascending 64 smallest so far; cand: 64 new keys.  Returns the
-// ascending 64 smallest of the union.
-__device__ __forceinline__ u64 wave_merge_smallest_key(u64 best, u64 cand, int lane) {
-  const u64 s = wave_sort_key(cand, lane);
-  const u64 r = __shfl(s, 63 - lane, 64);
-  u64 m = r < best ? r : best;  // bitonic, holds the 64 smallest
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const u64 p = __shfl_xor(m, j, 64);
-    m = (lane & j) == 0 ? (p < m ? p : m) : (p > m ? p : m);
-  }
-  return m;
-}
-
-__global__ __launch_bounds__(NT) void knn_kernel(int N, int d, int kk, const float* __restrict__ X,
-                                                 float* __restrict__ d2out, int32_t* __restrict__ idxout) {
-  __shared__ __attribute__((aligned(16))) float xr[DC * XR_LD];
-  __shared__ float xc[64 * XC_LD];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int row0 = blockIdx.x * RA;
-  const int nch = (d + DC - 1) / DC, ntile = (N + 63) / 64;
-
-  u64 best[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) best[u] = ~0ull;
-
-  float pre_r[TQ], pre_c[TQ];
-  fetch_tile_a(pre_r, X, row0, N, d, 0, tid);
-  fetch_tile_a(pre_c, X, 0, N, d, 0, tid);
-  float acc[16];
-  const int steps = ntile * nch;
-  for (int it = 0; it < steps; ++it) {
-    const int jt = it / nch, ch = it - jt * nch;
-    // a single-chunk row tile stays resident for the whole column walk
-    if (nch > 1 || it == 0) put_rows_a(xr, pre_r, tid);
-    put_cols_a(xc, pre_c, tid);
-    __syncthreads();
-    if (it + 1 < steps) {  // next step's tiles, in flight during the arithmetic below
-      const int jn = (it + 1) / nch, cn = (it + 1) - jn * nch;
-      if (nch > 1) fetch_tile_a(pre_r, X, row0, N, d, cn * DC, tid);
-      fetch_tile_a(pre_c, X, jn * 64, N, d, cn * DC, tid);
-    }
-    if (ch == 0) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc[u] = 0.f;
-    }
-    accumulate_a(acc, xr, xc, w, lane);
-    __syncthreads();
-    if (ch != nch - 1) continue;
-    const int j = jt * 64 + lane;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const u64 cand = j < N ? ((u64)__float_as_uint(acc[u]) << 32) | (u64)(uint32_t)j : ~0ull;
-      const u64 thr = __shfl(best[u], kk - 1, 64);
-      if (__any(cand < thr)) best[u] = wave_merge_smallest_key(best[u], cand, lane);  // wave-uniform branch
-    }
-  }
-  // k <= N, so the first k keys of every row are real candidates
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int i = row0 + w * 16 + u;
-    if (i < N && lane < kk) {
-      d2out[(long)i * kk + lane] = __uint_as_float((uint32_t)(best[u] >> 32));
-      idxout[(long)i * kk + lane] = (int32_t)(uint32_t)(best[u] & 0xffffffffull);
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // smooth_knn_dist + membership strengths
@@ -162,15 +70,8 @@ __global__ __launch_bounds__(FIN_NT) void umap_total_kernel(int N, const double*
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int q = tid; q < N; q += FIN_NT) s += rowsum[q];
-  s = wave_sum_d(s);
-  if ((tid & 63) == 0) slot[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < FIN_NT / 64; ++q) t += slot[q];
-    *total = t;
-  }
+  s = block_sum_d(s, slot, tid);
+  if (tid == 0) *total = s;
 }
 
 __global__ __launch_bounds__(NT) void umap_fuzzy_kernel(int N, int k, int ld, const float* __restrict__ d2,
@@ -312,16 +213,6 @@ __global__ __launch_bounds__(NT) void umap_epoch_kernel(int N, const int32_t* __
 
 extern "C" {
 
-int ssip_knn(int N, int d, int k, const float* X, float* d2, int32_t* idx, void* stream) {
-  SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_knn: N = %d outside 2..%d", N, UMAP_MAX_N);
-  SSIP_REQUIRE(d >= 1 && d <= 512, SSIP_ERR_ARG, "ssip_knn: d = %d outside 1..512", d);
-  SSIP_REQUIRE(k >= 2 && k <= KNN_MAX_K, SSIP_ERR_ARG, "ssip_knn: k = %d outside 2..%d", k, KNN_MAX_K);
-  SSIP_REQUIRE(k <= N, SSIP_ERR_ARG, "ssip_knn: k = %d neighbours asked of N = %d points", k, N);
-  SSIP_REQUIRE(X && d2 && idx, SSIP_ERR_ARG, "ssip_knn: null pointer");
-  SSIP_KLAUNCH(knn_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, k, X, d2, idx);
-  return ssip::check_launch("ssip_knn");
-}
-
 int64_t ssip_umap_workspace_bytes(int64_t N) {
   SSIP_REQUIRE(N >= 2 && N <= UMAP_MAX_N, SSIP_ERR_ARG, "ssip_umap_workspace_bytes: N = %ld outside 2..%d", (long)N,
                UMAP_MAX_N);
@@ -335,11 +226,7 @@ int ssip_umap_fuzzy(int N, int k, int ld, const float* d2, const int32_t* idx, f
                k, KNN_MAX_K, N);
   SSIP_REQUIRE(ld >= k, SSIP_ERR_ARG, "ssip_umap_fuzzy: leading dimension %d below k = %d", ld, k);
   SSIP_REQUIRE(d2 && idx && rho && sigma && memb, SSIP_ERR_ARG, "ssip_umap_fuzzy: null pointer");
-  SSIP_REQUIRE(workspace != nullptr, SSIP_ERR_ARG, "ssip_umap_fuzzy: null workspace");
-  SSIP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SSIP_ERR_ARG,
-               "ssip_umap_fuzzy: workspace must be 16-byte aligned");
-  SSIP_REQUIRE(workspace_bytes >= umap_ws_bytes(N), SSIP_ERR_WORKSPACE,
-               "ssip_umap_fuzzy: workspace of %ld bytes, need %ld", (long)workspace_bytes, umap_ws_bytes(N));
+  if (int rc = check_workspace("ssip_umap_fuzzy", workspace, workspace_bytes, umap_ws_bytes(N))) return rc;
   const UmapWs ws = umap_ws(workspace, N);
   const dim3 grid((N + NT / 64 - 1) / (NT / 64));
   SSIP_KLAUNCH(umap_rowsum_kernel, grid, dim3(NT), 0, (hipStream_t)stream, N, k, ld, d2, ws.rowsum);

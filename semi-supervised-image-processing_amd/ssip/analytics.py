@@ -21,8 +21,9 @@ csrc/analytics.hip; what stays on the host is the control flow around them:
   sklearn's two-phase schedule of gradient and momentum / gains steps with one
   read-back of four scalars on every 50th iteration and nothing else crossing
   the bus.
-* ``umap_fit`` is umap-learn's algorithm with its own kernels (csrc/umap.hip):
-  exact kNN, ``smooth_knn_dist`` and the membership strengths on the backend,
+* ``umap_fit`` is umap-learn's algorithm with its own kernels: exact kNN (a
+  pairwise kernel of csrc/analytics.hip), ``smooth_knn_dist`` and the
+  membership strengths (csrc/umap.hip, like the epochs) on the backend,
   the fuzzy union / curve fit / schedule / init on the host (O(N k)), then the
   layout epochs on the backend in Jacobi order with hashed negative samples.
 
@@ -133,6 +134,14 @@ def _relocate_empty(X: np.ndarray, labels: np.ndarray, mind2: np.ndarray, old: n
     return new.astype(old.dtype)
 
 
+def _float_matrix(X) -> np.ndarray:
+    """X as an array of float32 or float64: every other dtype becomes float64."""
+    X = np.asarray(X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    return X
+
+
 def _same_clustering(a: np.ndarray, b: np.ndarray, k: int) -> bool:
     """True when the labels of a map one-to-one onto those of b (sklearn's
     check before it lets a later init replace the best one)."""
@@ -149,10 +158,7 @@ class NumpyBackend:
     name = "cpu"
 
     def __init__(self, X: np.ndarray):
-        X = np.asarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self.X = np.ascontiguousarray(X)
+        self.X = np.ascontiguousarray(_float_matrix(X))
         self.n, self.d = self.X.shape
 
     def _row_chunks(self, cols: int):
@@ -497,6 +503,13 @@ class DeviceBackend:
     def _p(self, t):
         return self._lib.ptr(t)
 
+    def _workspace(self, query: str, *args):
+        """(device buffer, its size) of as many bytes as the library's ``query`` entry point asks for."""
+        nbytes = int(self._lib.call(query, *args))
+        if nbytes < 0:
+            self._lib.check(nbytes, query)
+        return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.dev), nbytes
+
     # -- K-Means --------------------------------------------------------------
     def begin(self, centres: np.ndarray) -> None:
         t = self._torch
@@ -507,10 +520,7 @@ class DeviceBackend:
         self._labels = t.full((self.n,), -1, dtype=t.int32, device=self.dev)
         self._prev = t.full((self.n,), -1, dtype=t.int32, device=self.dev)
         self._mind2 = t.empty(self.n, dtype=t.float32, device=self.dev)
-        self._ws_bytes = int(self._lib.call("ssip_kmeans_workspace_bytes", self.n, self.d, k))
-        if self._ws_bytes < 0:
-            self._lib.check(self._ws_bytes, "ssip_kmeans_workspace_bytes")
-        self._ws = t.empty(self._ws_bytes, dtype=t.uint8, device=self.dev)
+        self._ws, self._ws_bytes = self._workspace("ssip_kmeans_workspace_bytes", self.n, self.d, k)
         self._counts = t.empty(k, dtype=t.int32, device=self.dev)
         self._scalars = t.empty(4, dtype=t.float64, device=self.dev)
 
@@ -577,10 +587,7 @@ class DeviceBackend:
         t = self._torch
         if getattr(self, "_tws", None) is not None:
             return
-        self._tws_bytes = int(self._lib.call("ssip_tsne_workspace_bytes", self.n))
-        if self._tws_bytes < 0:
-            self._lib.check(self._tws_bytes, "ssip_tsne_workspace_bytes")
-        self._tws = t.empty(self._tws_bytes, dtype=t.uint8, device=self.dev)
+        self._tws, self._tws_bytes = self._workspace("ssip_tsne_workspace_bytes", self.n)
         self.P = t.empty((self.n, self.n), dtype=t.float32, device=self.dev)
         self._beta = t.empty(self.n, dtype=t.float64, device=self.dev)
         self._tscalars = t.empty(4, dtype=t.float64, device=self.dev)
@@ -632,7 +639,7 @@ class DeviceBackend:
     def tsne_p(self) -> np.ndarray:
         return self.P.cpu().numpy()
 
-    # -- native UMAP (csrc/umap.hip) -------------------------------------------
+    # -- native UMAP (kNN: csrc/analytics.hip, the rest: csrc/umap.hip) ----------
     def knn(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
         t = self._torch
         k = _check_k(k, self.n)
@@ -660,10 +667,7 @@ class DeviceBackend:
         k = _check_k(k, self.n)
         if self.knn_columns() < k:
             raise ValueError(f"ssip.analytics: umap_fuzzy({k}) needs a kNN result of at least {k} columns")
-        ws_bytes = int(self._lib.call("ssip_umap_workspace_bytes", self.n))
-        if ws_bytes < 0:
-            self._lib.check(ws_bytes, "ssip_umap_workspace_bytes")
-        ws = t.empty(ws_bytes, dtype=t.uint8, device=self.dev)
+        ws, ws_bytes = self._workspace("ssip_umap_workspace_bytes", self.n)
         rho = t.empty(self.n, dtype=t.float32, device=self.dev)
         sigma = t.empty(self.n, dtype=t.float32, device=self.dev)
         memb = t.empty((self.n, k), dtype=t.float32, device=self.dev)
@@ -746,9 +750,7 @@ def kmeans_fit(X: np.ndarray, k: int, n_init: int = 10, seed: int = 42, device: 
     """(labels int32 [N], inertia, centres [k][d]) of KMeans(n_clusters=k, n_init, random_state=seed)."""
     from sklearn.cluster import kmeans_plusplus
 
-    X = np.asarray(X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float64)
+    X = _float_matrix(X)
     if device == "cuda":
         X = X.astype(np.float32, copy=False)
     if not 2 <= int(k) <= 64:
@@ -839,9 +841,7 @@ def tsne_fit(X: np.ndarray, perplexity: float, seed: int = 42, max_iter: int = 1
 
     The scalars are read back on the error iterations only; nothing else
     synchronises host and device inside the loop."""
-    X = np.asarray(X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float64)
+    X = _float_matrix(X)
     n = X.shape[0]
     if not 2 <= n <= TSNE_MAX_N:
         raise ValueError(f"ssip.analytics: exact t-SNE supports 2 <= N <= {TSNE_MAX_N} (got {n}): P is N^2 floats")
@@ -1088,9 +1088,7 @@ def umap_fit(X: np.ndarray, n_neighbors: int, min_dist: float, seed: int = 42, n
     RNG).  ``knn`` = a precomputed ``(d2, idx)`` of at least ``n_neighbors``
     columns; a backend that already holds one (``backend.knn``) is reused.
     ``info``: a, b, n_epochs, n_edges (directed, after pruning), init."""
-    X = np.asarray(X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float64)
+    X = _float_matrix(X)
     n = X.shape[0]
     k = _check_k(n_neighbors, n)
     backend = backend if backend is not None else make_backend(X, device)

@@ -221,6 +221,30 @@ def test_kth_distance(dev, n, d):
         assert err <= BOUND_KTH, (n, d, k)
 
 
+@pytest.mark.parametrize("n", (2, 63, 64, 65, 257))
+@pytest.mark.parametrize("d", (2, 33, 50))
+def test_kth_distance_and_knn_share_the_walk_and_the_selection(dev, n, d):
+    """ssip_pairwise_kth and ssip_knn are two instantiations of one selection
+    over one column walk (csrc/pairwise_tile.h), so the k-th distance is the
+    root of column k - 1 of the kNN result bit for bit (both roots are
+    correctly rounded fp32), and a k result is a prefix of the widest one."""
+    from ssip import analytics as A
+
+    rng = np.random.default_rng(23 * n + d)
+    x = rng.normal(size=(n, d)).astype(np.float32)
+    x[n // 2] = x[0]  # a duplicate: equal distances, ordered by index
+    be = A.DeviceBackend(x)
+    wide_d2, wide_idx = be.knn(min(64, n))  # knn(64) wherever the input has 64 rows
+    for k in (2, 15, 64):
+        if k > n:
+            continue
+        d2, idx = be.knn(k)
+        assert d2.dtype == np.float32 and d2.shape == (n, k)
+        assert be.kth(k).astype(np.float32).tobytes() == np.sqrt(d2[:, k - 1]).tobytes(), (n, d, k)
+        assert np.ascontiguousarray(wide_d2[:, :k]).tobytes() == d2.tobytes(), (n, d, k)
+        assert np.ascontiguousarray(wide_idx[:, :k]).tobytes() == idx.tobytes(), (n, d, k)
+
+
 def _labelings():
     rng = np.random.default_rng(3)
     out = {}
@@ -274,7 +298,8 @@ def test_every_kernel_is_bit_reproducible(dev):
         be, scal = _run_lloyd_step(A, x, c)
         deg, bm = be.eps_graph(eps)
         return [be.labels(), be._mind2.cpu().numpy(), be.Cn.cpu().numpy(),
-                be._counts.cpu().numpy(), np.array(scal), deg, bm, be.kth(15), be.cluster_sums(enc, order, 5)]
+                be._counts.cpu().numpy(), np.array(scal), deg, bm, be.kth(15), *be.knn(15),
+                be.cluster_sums(enc, order, 5)]
 
     a, b = once(), once()
     for u, v in zip(a, b):
