@@ -139,14 +139,16 @@ int ssip_conv_wgrad(const ssip_conv_desc* d, int dtype, const void* dy, const vo
 /* The same with a workgroup budget for the split-K grid of the LDS-DMA wgrad
  * (ABI 10), for a wgrad that shares the chip with another stream's kernels
  * (the backward's side stream beside the dgrad / BN-backward chain); 0 =
- * ssip_conv_wgrad's full-chip grid.  By default a budget keeps the full-grid
- * tiles and sets their split count to ceil(max_workgroups / output tiles).
- * Only with $SSIP_WGRAD_BIG=1 (or 2: the K % 256 == 0 shapes only) does the
- * bf16 wgrad take 16-wave 256x256 / 128x256 tiles that fit one workgroup per
- * CU, at most max_workgroups of them (split count = floor(max_workgroups /
- * output tiles)); they measured faster alone but slower in the step.  The persistent
- * layer-1 and stem wgrads (one workgroup per CU, all of its LDS) run on at
- * most max_workgroups CUs.  Same result up to the fp32 order of the split /
+ * ssip_conv_wgrad's full-chip grid.  Under a budget the bf16 wgrad of a conv
+ * with K % 128 == 0 and R S C >= 512 takes 8-wave tiles that fit one
+ * workgroup per CU -- 256x256 where K and R S C are multiples of 256, else
+ * 128x256 -- on 62 % of the budget: split count = floor(floor(max_workgroups *
+ * 62 / 100) / output tiles), the other CUs left to the other stream.  Every
+ * other wgrad (and all of them with $SSIP_WGRAD_BIG=0) keeps the full-grid
+ * tiles, two workgroups per CU, with split count = ceil(max_workgroups /
+ * output tiles).  (Either count is at least 1 and bounded by the slab size
+ * and 16 k-steps per split.)  The persistent layer-1 and stem wgrads (one
+ * workgroup per CU, all of its LDS) run on at most max_workgroups CUs.  Same result up to the fp32 order of the split /
  * slab sum (fixed for a budget).  The workspace a budget needs:
  * ssip_conv_wgrad_workspace_bytes_budget (ABI 12; budget 0 =
  * ssip_conv_wgrad_workspace_bytes) -- a budget may need more slab bytes than

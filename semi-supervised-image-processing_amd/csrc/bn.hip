@@ -441,22 +441,8 @@ int ssip_bn_finalize(int C, int tiles, float* partial, const float* gamma, const
                    mean_out, invstd_out, scale_out, shift_out};
   const int S = fin_splits(tiles);
   double* scratch = fin_scratch(partial, (int64_t)C * tiles * 3);
-  // SSIP_FIN64=1: one-wave, LDS-free workgroups where one per channel
-  // suffices.  They fit beside a persistent kernel that holds a CU's whole LDS
-  // (the other stream's layer-1 halo conv), where a 256-thread workgroup with
-  // its 96-B combine waits for it to finish: layer-1 finalize 42 -> 20 us in
-  // the step trace, but the step moved -0.55 % on one box and +0.8 % on
-  // another (round 5): off by default.
-  static const bool nt64 = [] {
-    const char* e = getenv("SSIP_FIN64");
-    return e != nullptr && e[0] == '1';
-  }();
-  if (nt64 && S == 1)
-    SSIP_KLAUNCH(bn_finalize_kernel<64>, dim3(S, C), dim3(64), 0, st, C, tiles, S, (const float*)partial,
-                       scratch, f);
-  else
-    SSIP_KLAUNCH(bn_finalize_kernel<FIN_NT>, dim3(S, C), dim3(FIN_NT), 0, st, C, tiles, S,
-                       (const float*)partial, scratch, f);
+  SSIP_KLAUNCH(bn_finalize_kernel<FIN_NT>, dim3(S, C), dim3(FIN_NT), 0, st, C, tiles, S, (const float*)partial,
+               scratch, f);
   if (S > 1)
     SSIP_KLAUNCH(bn_finalize_merge_kernel, dim3((C + FIN_NT / 64 - 1) / (FIN_NT / 64)), dim3(FIN_NT), 0, st,
                        C, S, (const double*)scratch, f);

@@ -28,7 +28,6 @@
 // (bitwise reproducible, no atomics).
 #include <algorithm>
 #include <cstdio>
-#include <vector>
 #include "ssip_common.h"
 #include "fin_split.h"
 
@@ -108,7 +107,6 @@ struct ConvArgs {
   uint32_t a2_bytes, b2_bytes;
   int ds_from;
   int xcd_remap;  // 1: XCD-aware workgroup -> tile order (LDS-DMA kernel)
-  int dma_mid;  // LDS-DMA ring: the next stage's pieces after the k-step's reads, before its second MFMA half (SSIP_DMA_MID)
   int stagger;  // LDS-DMA ring: waves NW/2.. run each k-step's second MFMA half after the next barrier (SSIP_STAGGER)
   // INBN (LDS-DMA ring, FWD's A / WGRAD's B operand): the conv input is
   // relu(fma(y, in_scale[c], in_shift[c])) of the layer below, formed in place
@@ -1456,7 +1454,7 @@ __global__ void __launch_bounds__(64 * WMW * WNW, glds_min_waves(BM, BN, WMW * W
         for (int j = 0; j < FN; ++j) mma(acc[i][j], fa[1][i], fb[1][j]);
     }
     const bool refill = ks + NSTAGE - 1 < nsteps;
-    if (refill && !a.dma_mid) issue(ks + NSTAGE - 1, stage == 0 ? NSTAGE - 1 : stage - 1);
+    if (refill) issue(ks + NSTAGE - 1, stage == 0 ? NSTAGE - 1 : stage - 1);
     const char* As = smem + stage * STAGE;
     const char* Bs = As + A_BYTES;
     // both k-halves' fragments are requested before the first MFMA, so the
@@ -1493,9 +1491,6 @@ __global__ void __launch_bounds__(64 * WMW * WNW, glds_min_waves(BM, BN, WMW * W
           for (int j = 0; j < FN; ++j) read_mfrag<BN>(fb[1][j], Bs, wn * WTN + j * 16, lane, 1);
         }
       }
-      // (dma_mid: after every fragment read of the step, so no read follows
-      // the DMA into the ring before the next step's barrier)
-      if (h == 1 && refill && a.dma_mid) issue(ks + NSTAGE - 1, stage == 0 ? NSTAGE - 1 : stage - 1);
       if (h == 1 && lag) break;  // deferred past the next barrier
 #pragma unroll
       for (int i = 0; i < FM; ++i)
@@ -1741,13 +1736,6 @@ struct HaloArgs {
   // in_shift)) is formed in LDS (ssip_conv_fwd_bnrelu_in)
   const float *in_scale, *in_shift;
   __bf16* zout;  // INBN (nullable): the transformed input's own tile rows written out (the wgrad's x)
-  unsigned long long* stamps;  // STAMP instances only (SSIP_HALO_DIAG 128): per wave and tile 3 s_memtime stamps;
-                               // with it, 1 = no output stores, 2 = no MFMAs (compile-time forms, results wrong)
-  int diag;  // timing ablations only (SSIP_HALO_DIAG, results wrong): 4 no input-row DMA after the
-             // first tile, 8 no BN statistics (round 5's 1 = no stores / 2 = no MFMAs: r5_halo_lab.txt);
-             // 16 (results right): the next tile's rows issued before the MFMAs, not among them;
-             // 32 (results right, INBN): the BN+ReLU transform after the k-loop, not inside it;
-             // 64 (INBN, results wrong): no transform
 };
 
 constexpr int HALO_XBUF = 44 * 1024;
@@ -1763,16 +1751,6 @@ __device__ __forceinline__ int xtile_off(int px, int slot) { return px * 128 + (
 // LDS-only workgroup barrier: __syncthreads() would also drain vmcnt, i.e.
 // wait for the next tile's rows in flight and this tile's output stores
 __device__ __forceinline__ void halo_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }  // one input-row buffer: (TR + 2) * (W + 2) <= 352 pixels
-
-// diagnostic phase stamp (conv_halo_kernel<..., STAMP>): one asm statement with
-// its own lgkmcnt(0) (s_memtime returns out of order with LDS reads), fenced
-__device__ __forceinline__ unsigned long long halo_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
 
 // conv_halo_kernel's DGRAD epilogue with the BN-backward reduction of the
 // BN+ReLU below fused in (ssip_conv_dgrad_bn): per row-fragment i, the
@@ -1848,7 +1826,7 @@ __device__ __forceinline__ void halo_bnpost_epilogue(const HaloArgs& a, const f3
 // mask from the BN affine (y is the only extra operand: one load batch per
 // tile); 2 = any other post-op operand set (one load batch per row group:
 // the registers hold no more without spilling)
-template <int WMW, int WNW, bool FOLD = false, int BNPOST = 0, bool ADD = false, bool INBN = false, int STAMP = 0>
+template <int WMW, int WNW, bool FOLD = false, int BNPOST = 0, bool ADD = false, bool INBN = false>
 __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_kernel(const HaloArgs a) {
   typedef __bf16 T;
   constexpr int NW = WMW * WNW, NT = 64 * NW;
@@ -1905,7 +1883,6 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
     load_f8(ish, a.in_shift + c0);
   }
   auto xform_x = [&](int tile, char* Xs, bool zst) {
-    if (a.diag & 64) return;  // ablation: no transform (results wrong)
     const int R0 = tile * a.TR;
     const int n = R0 / a.H, p0 = R0 - n * a.H;
     for (int i = wave; i < nxi; i += NW) {
@@ -2025,7 +2002,7 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
     issue_w(jn);
     issue_x(u0 - jn * a.tiles, smem + B_BYTES);
   }
-  const bool stats = a.partial && wrows > 0 && !(a.diag & 8);
+  const bool stats = a.partial && wrows > 0;
   constexpr bool has_add = ADD;  // BNPOST == 0: out += add (BNPOST reads a.add itself)
   // The epilogue of one row group i of a finished tile: BN statistics over the
   // fp32 accumulators of its valid rows, then 16-bit stores straight from the
@@ -2047,7 +2024,7 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
         float t = FOLD ? ac[i][jj][e] + bcol : ac[i][jj][e];
         if (has_add) t = to_f32(from_f32<T>(t)) + to_f32(__builtin_bit_cast(T, ra[i][jj][e]));
         const T o = from_f32<T>(FOLD ? fmaxf(t, lo) : t);
-        if constexpr (!(STAMP & 4)) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, o), rsO, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, o), rsO, off, 0, 0);
       }
     }
   };
@@ -2101,8 +2078,6 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
     }
     first = false;
     halo_lds_barrier();
-    unsigned long long st0 = 0, st1 = 0;
-    if constexpr (STAMP) st0 = halo_stamp();
     const int un = u + 1;
     const bool more = un < u1;
     const int jn_next = more ? un / a.tiles : jn;
@@ -2125,10 +2100,8 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
     // reads): one piece per wave after every other k-step's MFMAs, so the
     // DMA issue (~60-185 cycles a piece) runs beside the matrix pipe instead
     // of ahead of it with the partner wave's in the same place
-    const bool spread = prefetch && !(a.diag & 4) && !(a.diag & 16);
     const int nR0 = (un - jn * a.tiles) * a.TR;
     const int nn = nR0 / a.H, np0 = nR0 - nn * a.H;
-    if (prefetch && !(a.diag & 4) && (a.diag & 16)) issue_x(un - jn * a.tiles, Xn);
 
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -2167,7 +2140,7 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
       for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int jj = 0; jj < FN; ++jj)
-          if constexpr (!(STAMP & 2)) mma(acc[i][jj], fa[st & 1][i], fb[st & 1][jj]);
+          mma(acc[i][jj], fa[st & 1][i], fb[st & 1][jj]);
       if (st % 2 == 0 && st / 2 < XPW) {
         const int i = wave + (st / 2) * NW;
         if constexpr (INBN) {
@@ -2179,33 +2152,28 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
           // so the compiler can count the loads in flight: vmcnt(XLAG) before
           // a store instead of vmcnt(0))
           xreg_load(nn, np0, i, (st / 2) % (XLAG + 1), a.zout != nullptr && jn == 0);
-          if ((a.diag & 32) && spread && i < nxi) issue_x_piece(nn, np0, i, Xn);
         } else {
-          if (spread && i < nxi) issue_x_piece(nn, np0, i, Xn);
+          if (prefetch && i < nxi) issue_x_piece(nn, np0, i, Xn);
         }
       }
       if constexpr (INBN) {
         if (st % 2 == 0 && st / 2 >= XLAG && st / 2 - XLAG < XPW) {
           const int k = st / 2 - XLAG, i = wave + k * NW;
-          if (spread && !(a.diag & 32) && i < nxi) xreg_store(i, k % (XLAG + 1), Xn);
+          if (prefetch && i < nxi) xreg_store(i, k % (XLAG + 1), Xn);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // the next tile's rows (issued before the MFMAs) and this wave's older
+    // the next tile's rows (issued among the MFMAs) and this wave's older
     // stores retire here; nothing younger is in flight
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (STAMP) st1 = halo_stamp();
     if constexpr (INBN) {
       // pieces staged too late for the k-loop's stores (XPW + XLAG > 9)
 #pragma unroll
       for (int k = 9 - XLAG; k < XPW; ++k) {
         const int i = wave + k * NW;
-        if (spread && !(a.diag & 32) && k >= 0 && i < nxi) xreg_store(i, k % (XLAG + 1), Xn);
+        if (prefetch && k >= 0 && i < nxi) xreg_store(i, k % (XLAG + 1), Xn);
       }
-      // DMA'd pieces (diag 32, or the non-spread order) are transformed in place
-      if (prefetch && !(a.diag & 4) && ((a.diag & 32) || !spread))
-        xform_x(un - jn * a.tiles, Xn, a.zout != nullptr && jn == 0);
     }
 
     // ---- epilogue
@@ -2239,15 +2207,6 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 4) conv_halo_ker
       for (int i = 0; i < FM; ++i) epi_rows(acc, i, tile, jn, rap);
       if (stats && !prefetch) stats_flush(jn);
     }
-    if constexpr (STAMP) {
-      const unsigned long long st2 = halo_stamp();
-      if (lane == 0 && u - u0 < 32) {
-        unsigned long long* sp = a.stamps + (((long)g * NW + wave) * 32 + (u - u0)) * 3;
-        sp[0] = st0;
-        sp[1] = st1;
-        sp[2] = st2;
-      }
-    }
     if (more && !prefetch) {
       // panel change: new weights and the next tile's rows, loaded once every
       // wave is past this tile's MFMAs
@@ -2280,7 +2239,6 @@ struct StemArgs {
   float* partial;     // BN records (nullable)
   uint32_t x_bytes, w_bytes, o_bytes;
   int N, H, W, P, Q, Ncols, tiles, units;
-  int diag;  // timing ablations only (SSIP_STEM_DIAG, results wrong): 1 no output stores, 8 no BN statistics
 };
 
 constexpr int STEM_QP = 128, STEM_TR = 2, STEM_XROWS = 2 * STEM_TR + 5;
@@ -2412,7 +2370,7 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 2) conv_stem_hal
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    if (a.partial && wrows > 0 && !(a.diag & 8)) {
+    if (a.partial && wrows > 0) {
       // per-lane shifted sums over the fp32 accumulators of the valid rows;
       // merged across the wave (and written) when the panel or range ends
       ws.tile(acc, vmask);
@@ -2432,17 +2390,15 @@ __global__ void __launch_bounds__(64 * WMW * WNW, (WMW * WNW) / 2) conv_stem_hal
         ws.reset();
       }
     }
-    if (!(a.diag & 1)) {
-      const uint32_t obase = (uint32_t)(((long)tile * STEM_TR * a.Q * a.Ncols + jn * BN) * 2);
+    const uint32_t obase = (uint32_t)(((long)tile * STEM_TR * a.Q * a.Ncols + jn * BN) * 2);
 #pragma unroll
-      for (int i = 0; i < FM; ++i)
+    for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int jj = 0; jj < FN; ++jj)
+      for (int jj = 0; jj < FN; ++jj)
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, from_f32<T>(acc[i][jj][e])), rsO,
-                                                  obase + rowoff[i][e] + jj * 32, 0, 0);
-    }
+        for (int e = 0; e < 4; ++e)
+          __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, from_f32<T>(acc[i][jj][e])), rsO,
+                                                obase + rowoff[i][e] + jj * 32, 0, 0);
     if (more && !prefetch) {
       halo_lds_barrier();
       issue_w(jn_next);
@@ -2471,7 +2427,6 @@ struct HaloWgArgs {
   float* slab;       // [G][64][576]
   uint32_t x_bytes;
   int N, H, W, TR, tiles;
-  int spread;        // the next tile's pieces among the k-steps' MFMAs (SSIP_HWG_SPREAD=0: ahead of them)
   // INBN: X is y of the BN+ReLU below; relu(fma(y, in_scale, in_shift)) is
   // formed in LDS (ssip_conv_wgrad_bnrelu_in)
   const float *in_scale, *in_shift;
@@ -2639,13 +2594,11 @@ __global__ void __launch_bounds__(512, 2) conv_halo_wgrad_kernel(const HaloWgArg
     halo_lds_barrier();
     // the next tile's pieces: two per wave after each of k-steps 0-4's MFMAs
     // (beside the matrix pipe instead of ahead of it, where both waves of a
-    // SIMD issued theirs at once; SSIP_HWG_SPREAD=0: ahead, as before)
+    // SIMD issued theirs at once)
     const bool nxt = u + 1 < u1;
-    if (nxt && !a.spread) issue(u + 1, Xn, Xn + HWG_XBUF);
     const int nR0 = (u + 1) * a.TR;
     const int nn = nR0 / a.H, np0 = nR0 - nn * a.H;
     const int nbase = (nn * a.H + np0) * a.W * 128;
-    const bool spread = nxt && a.spread;
     Frag<T> fa[2][2], fb[2][9];
     auto load_step = [&](int ks, Frag<T>(&ra)[2], Frag<T>(&rb)[9]) {
 #pragma unroll
@@ -2661,7 +2614,7 @@ __global__ void __launch_bounds__(512, 2) conv_halo_wgrad_kernel(const HaloWgArg
       for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int b = 0; b < 9; ++b) mma(acc[x][b], fa[ks & 1][x], fb[ks & 1][b]);
-      if (ks < 5 && spread) {
+      if (ks < 5 && nxt) {
         issue_pc(2 * ks, nbase, np0, Xn, Xn + HWG_XBUF);
         issue_pc(2 * ks + 1, nbase, np0, Xn, Xn + HWG_XBUF);
       }
@@ -3142,22 +3095,55 @@ static void pick_tile(int M, int Ng, int elem_bytes, Plan& pl) {
 
 static bool glds_has(int mode, bool stem, int bm, int bn, int wm, int wn, int st);
 static int device_cus();
-// SSIP_WGRAD_BIG (a wgrad with a budget, i.e. on the side stream): 0 = the
-// full-grid tiles; 1 = 16-wave 256-column tiles for every 3x3 wgrad, 2 = only
-// the 256x256 ones (K % 256 == 0) -- round 5: faster alone, slower in the step
-// (6.34 vs 6.19 ms), a 16-wave workgroup holding every register of its CU
-// keeps the main stream's dgrad / BN chain off it; 3 = 8-wave 256x256 tiles
-// for those; 4 (default) = those and 8-wave 128x256 tiles where 128 <= K <
-// 256, both on SSIP_WGRAD_BIG_CUS (default 62) percent of the budget's CUs,
-// the rest of the chip left to the main stream.  Round 6, with the stagger
-// (tools/gpu_r6_{i,j,k}.sh, alternated runs on one box each, ms/step): mode 4
-// on 62 % of the CUs 5.937 vs 6.013 (4 + 4; 56 % 5.969, 70 % 5.979, 80 %
-// 6.083), 5.933 vs 6.018 on another box; mode 3 at 62 % 5.985; mode 3 on
-// every CU 5.98 vs 5.87 (profiles/r6_wgrad_big_ab.txt)
-static int wgrad_big_mode() {
-  const char* e = getenv("SSIP_WGRAD_BIG");
-  return e ? atoi(e) : 4;
+
+// The tuning knobs of this file, read from the environment on every call
+// (tests and labs flip them in one process): this file's only environment reads.
+// ssip/ops.py keys its plan cache on these names (tests/test_cpu_conv_knobs.py).
+struct ConvKnobs {
+  bool halo;           // SSIP_HALO (0: off): the halo / stem kernels where they apply
+  const char* force;   // SSIP_CONV_FORCE="<f|d|w>,bm,bn,waves_m,waves_n,stages" (apply_force), or null
+  int stagger;         // SSIP_STAGGER: pass mask (stagger_for)
+  bool wgrad_big;      // SSIP_WGRAD_BIG (0: the full-grid tiles for a wgrad with a budget)
+  int wgrad_blocks;    // SSIP_WGRAD_BLOCKS: target workgroup count of a wgrad (0: unset)
+  int bnrelu_glds;     // SSIP_BNRELU_GLDS: bit 0 the 1x1, bit 1 the 3x3 BN+ReLU-in ring form (glds_inbn_plan)
+  long bnrelu_minm;    // SSIP_BNRELU_GLDS_MINM: fewest rows for the 1x1 form
+  bool no_fwd_dsfuse;  // SSIP_NO_FWD_DSFUSE: conv + downsample forwards as two launches
+  // the halo / stem kernels may take pass 'f' / 'd' / 'w': not switched off, and
+  // no SSIP_CONV_FORCE for that pass (it selects the implicit-GEMM kernels)
+  bool halo_for(char pass) const { return halo && !(force && force[0] == pass); }
+};
+
+static ConvKnobs conv_knobs() {
+  ConvKnobs k;
+  const char* e = getenv("SSIP_HALO");
+  k.halo = !(e && e[0] == '0');
+  k.force = getenv("SSIP_CONV_FORCE");
+  e = getenv("SSIP_STAGGER");
+  k.stagger = e ? atoi(e) : 7;
+  e = getenv("SSIP_WGRAD_BIG");
+  k.wgrad_big = !e || atoi(e) != 0;
+  e = getenv("SSIP_WGRAD_BLOCKS");
+  k.wgrad_blocks = (e && e[0]) ? std::max(1, atoi(e)) : 0;
+  e = getenv("SSIP_BNRELU_GLDS");
+  k.bnrelu_glds = e ? atoi(e) : 1;
+  e = getenv("SSIP_BNRELU_GLDS_MINM");
+  k.bnrelu_minm = e ? atol(e) : 262144l;
+  k.no_fwd_dsfuse = getenv("SSIP_NO_FWD_DSFUSE") != nullptr;
+  return k;
 }
+
+// A wgrad with a budget (on the side stream) takes 8-wave 256x256 tiles, and
+// 8-wave 128x256 tiles where 128 <= K < 256, on WGRAD_BIG_CUS percent of the
+// budget's CUs, the rest of the chip left to the main stream; SSIP_WGRAD_BIG=0
+// keeps the full-grid tiles.  Round 6, with the stagger (tools/gpu_r6_{i,j,k}.sh,
+// alternated runs on one box each, ms/step): on 62 % of the CUs 5.937 vs 6.013
+// (4 + 4; 56 % 5.969, 70 % 5.979, 80 % 6.083), 5.933 vs 6.018 on another box;
+// the 256x256 tiles alone at 62 % 5.985, on every CU 5.98 vs 5.87
+// (profiles/r6_wgrad_big_ab.txt).  Measured and removed: 16-wave 256-column
+// tiles -- round 5: faster alone, slower in the step (6.34 vs 6.19 ms), a
+// 16-wave workgroup holding every register of its CU keeps the main stream's
+// dgrad / BN chain off it.
+constexpr int WGRAD_BIG_CUS = 62;
 
 // Default LDS-DMA configuration for a bf16 GEMM view (M x Ng, reduction Kg).
 // Chosen from tools/tune_conv.py over the ResNet-18 train-step shapes
@@ -3192,8 +3178,8 @@ static void choose_glds(int mode, const ConvArgs& a, Plan& pl) {
 
 // Tuning override: SSIP_CONV_FORCE="<f|d|w>,bm,bn,waves_m,waves_n,stages"
 // (stages 0 = register-staged kernel) applies to the named pass only.
-static int apply_force(int mode, int elem_bytes, Plan& pl) {
-  const char* e = getenv("SSIP_CONV_FORCE");
+static int apply_force(const ConvKnobs& k, int mode, int elem_bytes, Plan& pl) {
+  const char* e = k.force;
   if (!e || !e[0]) return SSIP_OK;
   const char want = mode == MODE_FWD ? 'f' : mode == MODE_DGRAD ? 'd' : 'w';
   if (e[0] != want || (pl.conv1 && !pl.stem_glds)) return SSIP_OK;
@@ -3213,24 +3199,22 @@ static int apply_force(int mode, int elem_bytes, Plan& pl) {
   return SSIP_OK;
 }
 
-// SSIP_STAGGER (read per plan, so a lab can flip it in one process): a
-// bit mask over the passes whose LDS-DMA ring kernels run the stagger
+// SSIP_STAGGER: a bit mask over the passes whose LDS-DMA ring kernels run the stagger
 // (conv_glds_kernel: waves NW/2.. one MFMA half behind), 1 fwd, 2 dgrad,
 // 4 wgrad; 0 off; default 7 (round 6, tools/stagger_lab.py, batch 256, same
 // bits: the layer 2-4 launches -3.8 % in sum, the 256x256 layer-3 fwd /
 // dgrad -11 to -13 %, the side stream's one-workgroup-per-CU wgrads -4 to
 // -6 %; step 6.076 -> 6.045 ms, 3 + 3 alternated runs,
 // profiles/r6_stagger_lab.txt).
-static int stagger_for(int mode, const Plan& pl) {
+static int stagger_for(const ConvKnobs& k, int mode, const Plan& pl) {
   if (pl.stages <= 0 || pl.conv1) return 0;
-  const char* e = getenv("SSIP_STAGGER");
-  const int m = e != nullptr ? atoi(e) : 7;
-  return (m >> mode) & 1;
+  return (k.stagger >> mode) & 1;
 }
 
 static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl, int wg_budget = 0,
                      bool allow_big = true) {
   SSIP_REQUIRE(desc_ok(d), SSIP_ERR_ARG, "bad conv descriptor");
+  const ConvKnobs k = conv_knobs();
   pl.mode = mode;
   pl.conv1 = (d->C == 4);
   // the padded stem stores S = 8 columns for a real 7-wide filter
@@ -3275,31 +3259,24 @@ static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl
   // workgroups of 256 columns hide that and halve the DMA bytes per FLOP
   // (tools/wgrad_lab.py at the 256-workgroup budget, profiles/r5_wgrad_lab.txt:
   // l2.3x3 110.9 -> 89.1 us with 128x256, l3.3x3 109.9 -> 73.9 and l4.3x3
-  // 101.4 -> 75.4 with 256x256) -- but not in the step (wgrad_big_mode)
-  const int bigm = (mode == MODE_WGRAD && allow_big) ? wgrad_big_mode() : 0;
+  // 101.4 -> 75.4 with 256x256) -- but not in the step (WGRAD_BIG_CUS)
   // (round 5 also measured 8-wave 128x256 tiles at the budget -- two waves
   // per SIMD, 96 KiB of LDS, so not the whole CU: 517.6 -> 461.1 us over the
   // six layer 2-4 wgrads, but the step 6.14 -> 6.43 ms, 4 + 4 runs)
-  if (mode == MODE_WGRAD && wg_budget > 0 && pl.stages > 0 && !pl.conv1 && bigm > 0) {
+  if (mode == MODE_WGRAD && wg_budget > 0 && pl.stages > 0 && !pl.conv1 && allow_big && k.wgrad_big) {
     // (the 1x1 downsample wgrads, Ng <= 256, keep their many-tile grids)
     if (a.M % 256 == 0 && a.Ng % 256 == 0 && a.Ng >= 512) {
-      // 3, 4: the 8-wave 256x256 tile (with the stagger: l3 / l4 3x3 wgrads
-      // at the budget 98 -> 73 us, profiles/r6_tile_lab.txt)
-      pl.bm = 256; pl.bn = 256; pl.wmw = 4; pl.wnw = bigm >= 3 ? 2 : 4;
-    } else if (bigm == 1 && a.M % 128 == 0 && a.Ng >= 512) {
-      pl.bm = 128; pl.bn = 256; pl.wmw = 4; pl.wnw = 4;  // a partial last tile where Ng % 256 != 0
-    } else if (bigm == 4 && a.M % 128 == 0 && a.Ng >= 512) {
-      pl.bm = 128; pl.bn = 256; pl.wmw = 2; pl.wnw = 4;  // 8 waves, 96 KiB of LDS
+      // the 8-wave 256x256 tile (with the stagger: l3 / l4 3x3 wgrads at the
+      // budget 98 -> 73 us, profiles/r6_tile_lab.txt)
+      pl.bm = 256; pl.bn = 256; pl.wmw = 4; pl.wnw = 2;
+    } else if (a.M % 128 == 0 && a.Ng >= 512) {
+      pl.bm = 128; pl.bn = 256; pl.wmw = 2; pl.wnw = 4;  // 8 waves, 96 KiB of LDS; a partial last tile where Ng % 256 != 0
     }
-    if (bigm >= 3 && pl.bn == 256) {
-      // on SSIP_WGRAD_BIG_CUS percent of the budget's CUs, the rest left to the
-      // main stream (measured: profiles/r6_tile_lab.txt)
-      const char* e = getenv("SSIP_WGRAD_BIG_CUS");
-      const int pc = e ? std::max(1, std::min(100, atoi(e))) : 62;
-      wg_budget = std::max(1, wg_budget * pc / 100);
-    }
+    // on WGRAD_BIG_CUS percent of the budget's CUs, the rest left to the
+    // main stream (measured: profiles/r6_tile_lab.txt)
+    if (pl.bn == 256) wg_budget = std::max(1, wg_budget * WGRAD_BIG_CUS / 100);
   }
-  if (int rc = apply_force(mode, elem_bytes, pl)) return rc;
+  if (int rc = apply_force(k, mode, elem_bytes, pl)) return rc;
   if (mode == MODE_WGRAD) {
     const int tiles = ceil_div(a.M, pl.bm) * ceil_div(a.Ng, pl.bn);
     const int total_ks = ceil_div(a.Mred, BK);
@@ -3313,8 +3290,8 @@ static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl
     const int cap_bytes = (int)std::max<long>(1, (64l << 20) / slab_split);
     const int max_splits = std::max(1, std::min(cap_bytes, total_ks / 16));
     int splits = 1;
-    if (const char* e = getenv("SSIP_WGRAD_BLOCKS"); e && e[0]) {  // tuning override: target workgroup count
-      splits = std::min(max_splits, ceil_div(std::max(1, atoi(e)), tiles));
+    if (k.wgrad_blocks > 0) {  // tuning override: target workgroup count
+      splits = std::min(max_splits, ceil_div(k.wgrad_blocks, tiles));
     } else if (pl.stages > 0 && wg_budget > 0) {
       // a wgrad sharing the chip (ssip_conv_wgrad_budget): ResNet-18 train
       // step with the side-stream wgrads at one workgroup per CU, two A/Bs of
@@ -3350,15 +3327,7 @@ static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl
   const int tiles_m = ceil_div(a.M, pl.bm);
   pl.grid = dim3(tiles_m * a.tiles_n, pl.splits, 1);
   a.xcd_remap = 1;
-  {
-    // SSIP_DMA_MID: 0 never, 1 every LDS-DMA ring, 2 the 256x256 tiles only
-    static const int mid = [] {
-      const char* e = getenv("SSIP_DMA_MID");
-      return e != nullptr ? atoi(e) : 0;
-    }();
-    a.dma_mid = mid == 1 || (mid == 2 && pl.bm == 256 && pl.bn == 256);
-  }
-  a.stagger = stagger_for(mode, pl);
+  a.stagger = stagger_for(k, mode, pl);
   return SSIP_OK;
 }
 
@@ -3366,11 +3335,8 @@ static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl
 // the ones choose_glds() selects (round 3's wider tuning sets are on the
 // r3-variants branch, with tools/tune_conv.py's lists)
 #define SSIP_GLDS_FD(X) X(128, 128, 4, 2, 2) X(128, 64, 4, 2, 2) X(256, 256, 4, 2, 2) X(128, 128, 4, 4, 3)
-// (the first two: the full-grid tiles; the two 16-wave ones: the side-stream
-// budget's; the rest are tools/wgrad_lab.py comparison points)
-#define SSIP_GLDS_WG(X)                                                                                     \
-  X(128, 128, 4, 2, 2) X(64, 128, 2, 4, 2) X(256, 256, 4, 4, 2) X(128, 256, 4, 4, 2) X(128, 256, 2, 4, 2)    \
-  X(256, 256, 4, 2, 2) X(128, 128, 4, 4, 2)
+// (the first two: the full-grid tiles; the other two: the side-stream budget's)
+#define SSIP_GLDS_WG(X) X(128, 128, 4, 2, 2) X(64, 128, 2, 4, 2) X(128, 256, 2, 4, 2) X(256, 256, 4, 2, 2)
 #define SSIP_GLDS_POST(X) X(128, 128, 4, 2, 2) X(128, 64, 4, 2, 2)
 #define SSIP_GLDS_FOLD(X) SSIP_GLDS_FD(X)
 #define SSIP_GLDS_STEM(X) X(128, 64, 4, 2, 2)
@@ -3593,10 +3559,7 @@ static int device_cus() {
 }
 
 static bool halo_plan(int mode, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  const char* e = getenv("SSIP_HALO");
-  if (e && e[0] == '0') return false;
-  const char* f = getenv("SSIP_CONV_FORCE");
-  if (f && f[0] == (mode == MODE_FWD ? 'f' : 'd')) return false;
+  if (!conv_knobs().halo_for(mode == MODE_FWD ? 'f' : 'd')) return false;
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 ||
       d->P != d->H || d->Q != d->W)
     return false;
@@ -3623,10 +3586,7 @@ static bool halo_plan(int mode, const ssip_conv_desc* d, int dtype, HaloPlan& hp
 
 // ---- stem path (conv_stem_halo_kernel): the pre-padded 7x7 / stride 2 stem
 static bool stem_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  const char* e = getenv("SSIP_HALO");
-  if (e && e[0] == '0') return false;
-  const char* f = getenv("SSIP_CONV_FORCE");
-  if (f && f[0] == 'f') return false;
+  if (!conv_knobs().halo_for('f')) return false;
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->C != 4 || d->R != 7 || d->S != 8 || d->stride != 2 || d->pad != 0 ||
       d->K % 64 != 0 || d->Q > STEM_QP || d->P % STEM_TR != 0 || d->W % 2 != 0 ||
       STEM_XROWS * d->W * 8 > STEM_XBUF || d->H < 2 * (d->P - 1) + 7)
@@ -3653,18 +3613,13 @@ static int launch_stem_halo(const ssip_conv_desc* d, const HaloPlan& hp, const v
   s.o_bytes = (uint32_t)((long)d->N * d->P * d->Q * d->K * 2);
   s.N = d->N; s.H = d->H; s.W = d->W; s.P = d->P; s.Q = d->Q; s.Ncols = d->K;
   s.tiles = hp.tiles; s.units = hp.units;
-  s.diag = 0;
-  if (const char* dg = getenv("SSIP_STEM_DIAG")) s.diag = atoi(dg);
   SSIP_KLAUNCH((conv_stem_halo_kernel<4, 2>), dim3(hp.G), dim3(512), 0, st, s);
   return ::ssip::check_launch("conv_stem_halo");
 }
 
 // ---- halo WGRAD (conv_halo_wgrad_kernel): 3x3 / stride 1 / pad 1, C = K = 64, bf16
 static bool halo_wg_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  const char* e = getenv("SSIP_HALO");
-  if (e && e[0] == '0') return false;
-  const char* f = getenv("SSIP_CONV_FORCE");
-  if (f && f[0] == 'w') return false;
+  if (!conv_knobs().halo_for('w')) return false;
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 ||
       d->P != d->H || d->Q != d->W || d->C != 64 || d->K != 64)
     return false;
@@ -3688,10 +3643,7 @@ static bool halo_wg_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
 
 // ---- stem WGRAD (conv_stem_wgrad_kernel)
 static bool stem_wg_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  const char* e = getenv("SSIP_HALO");
-  if (e && e[0] == '0') return false;
-  const char* f = getenv("SSIP_CONV_FORCE");
-  if (f && f[0] == 'w') return false;
+  if (!conv_knobs().halo_for('w')) return false;
   if (!stem_plan(d, dtype, hp) || d->K != 64) return false;  // same geometry as the forward's kernel
   hp.G = std::min(hp.tiles, device_cus());
   hp.units = hp.tiles;
@@ -3729,7 +3681,6 @@ static int launch_halo(int mode, const ssip_conv_desc* d, const HaloPlan& hp, co
   h.N = d->N; h.H = d->H; h.W = d->W; h.Ncols = hp.cols;
   h.TR = hp.TR; h.tiles = hp.tiles; h.units = hp.units;
   h.flip = mode == MODE_DGRAD ? 1 : 0;
-  if (const char* dg = getenv("SSIP_HALO_DIAG")) h.diag = atoi(dg);
   // 8 waves of 64x32 (16 waves of 32x32 were ~10 % faster in isolation but 3 %
   // slower in the step, where the side streams' kernels run beside them; 4
   // waves of 64x64 slower still: r3-variants branch)
@@ -3748,34 +3699,7 @@ static int launch_halo(int mode, const ssip_conv_desc* d, const HaloPlan& hp, co
     SSIP_KLAUNCH((conv_halo_kernel<4, 2, true>), dim3(hp.G), dim3(512), 0, st, h);
   else if (add != nullptr)
     SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, true>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (h.diag & 128) {
-    // phase stamps (lab only): per workgroup, wave and tile {after the tile's
-    // barrier, after the k-loop's vmcnt(0), after the epilogue}, written to
-    // SSIP_HALO_STAMP_OUT as raw u64 [G][8][32][3]
-    static unsigned long long* buf = nullptr;
-    const size_t n = (size_t)hp.G * 8 * 32 * 3;
-    if (buf == nullptr && hipMalloc(&buf, n * 8) != hipSuccess) return SSIP_ERR_LAUNCH;
-    (void)hipMemsetAsync(buf, 0, n * 8, st);
-    h.stamps = buf;
-    // compile-time ablations (timing only, results wrong): diag 2 no MFMAs, diag 1 no output stores
-    if ((h.diag & 3) == 3)
-      SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, false, false, 7>), dim3(hp.G), dim3(512), 0, st, h);
-    else if (h.diag & 2)
-      SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, false, false, 3>), dim3(hp.G), dim3(512), 0, st, h);
-    else if (h.diag & 1)
-      SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, false, false, 5>), dim3(hp.G), dim3(512), 0, st, h);
-    else
-      SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, false, false, 1>), dim3(hp.G), dim3(512), 0, st, h);
-    std::vector<unsigned long long> host(n);
-    if (hipMemcpyAsync(host.data(), buf, n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return SSIP_ERR_LAUNCH;
-    const char* path = getenv("SSIP_HALO_STAMP_OUT");
-    if (FILE* f = fopen(path ? path : "/tmp/halo_stamps.bin", "wb")) {
-      fwrite(host.data(), 8, n, f);
-      fclose(f);
-    }
-  } else
+  else
     SSIP_KLAUNCH((conv_halo_kernel<4, 2>), dim3(hp.G), dim3(512), 0, st, h);
   return ::ssip::check_launch("conv_halo");
 }
@@ -3795,11 +3719,6 @@ static int launch_halo_wgrad(const ssip_conv_desc* d, HaloPlan hp, const void* d
   h.slab = static_cast<float*>(workspace);
   h.x_bytes = (uint32_t)((long)d->N * d->H * d->W * 64 * 2);
   h.N = d->N; h.H = d->H; h.W = d->W; h.TR = hp.TR; h.tiles = hp.tiles;
-  static const int spread = [] {
-    const char* e = getenv("SSIP_HWG_SPREAD");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-  }();
-  h.spread = spread;
   h.in_scale = in_scale;
   h.in_shift = in_shift;
   if (in_scale != nullptr)
@@ -3857,7 +3776,7 @@ int ssip_conv_fwd(const ssip_conv_desc* d, int dtype, const void* x, const void*
 // downsample over the same input and output grid: one LDS-DMA launch when the
 // conv takes a 2- or 3-stage ring kernel (else false: two launches).
 static bool fwd_ds_plan(const ssip_conv_desc* d, const ssip_conv_desc* dds, int dtype, Plan& pl) {
-  if (dtype != SSIP_BF16 || !desc_ok(d) || !desc_ok(dds) || getenv("SSIP_NO_FWD_DSFUSE")) return false;
+  if (dtype != SSIP_BF16 || !desc_ok(d) || !desc_ok(dds) || conv_knobs().no_fwd_dsfuse) return false;
   if (d->R != 3 || d->S != 3 || d->pad != 1 || dds->R != 1 || dds->S != 1 || dds->pad != 0 ||
       dds->stride != d->stride || dds->N != d->N || dds->H != d->H || dds->W != d->W || dds->C != d->C ||
       dds->K != d->K || dds->P != d->P || dds->Q != d->Q || d->C % 64 != 0)
@@ -4000,24 +3919,17 @@ static int wgrad_implicit(Plan& pl, const ssip_conv_desc* d, int dtype, const vo
 // SSIP_BNRELU_GLDS: bit 0 the 1x1 / stride-1 form (default on: config 5,
 // 60.23 vs 60.60 ms/step with the forward's z_out, profiles/r6_bnrelu_in_glds_lab.txt),
 // bit 1 the 3x3 form (off: slower in both steps)
-static int bnrelu_glds_mask() {
-  const char* e = getenv("SSIP_BNRELU_GLDS");
-  return e != nullptr ? atoi(e) : 1;
-}
-
 static bool glds_inbn_plan(int mode, const ssip_conv_desc* d, int dtype, Plan& pl, int budget = 0) {
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->stride != 1 || d->C % 64 || d->C > GLDS_INBN_C || d->K % 64)
     return false;
-  const int m = bnrelu_glds_mask();
+  const ConvKnobs k = conv_knobs();
   // the 1x1 form pays where the apply pass it removes is large: per launch it
   // wins at ResNet-50 layers 1-2 (>= 262,144 rows) and loses at layers 3-4,
   // where the conv is short and the in-ring transform is not hidden
   // (profiles/r6_bnrelu_in_glds_lab.txt); SSIP_BNRELU_GLDS_MINM overrides
-  const char* me = getenv("SSIP_BNRELU_GLDS_MINM");
-  const long min_rows = me != nullptr ? atol(me) : 262144l;
-  if (d->R == 1 && (long)d->N * d->H * d->W < min_rows) return false;
-  const bool g1 = d->R == 1 && d->S == 1 && d->pad == 0 && (m & 1);
-  const bool g3 = d->R == 3 && d->S == 3 && d->pad == 1 && (m & 2);
+  if (d->R == 1 && (long)d->N * d->H * d->W < k.bnrelu_minm) return false;
+  const bool g1 = d->R == 1 && d->S == 1 && d->pad == 0 && (k.bnrelu_glds & 1);
+  const bool g3 = d->R == 3 && d->S == 3 && d->pad == 1 && (k.bnrelu_glds & 2);
   if (!g1 && !g3) return false;
   HaloPlan hp;
   if (halo_plan(MODE_FWD, d, dtype, hp)) return false;
@@ -4043,7 +3955,7 @@ static int dgrad_bn_plan(const ssip_conv_desc* d, int dtype, Plan& pl, HaloPlan&
   halo = halo_plan(MODE_DGRAD, d, dtype, hp);
   if (halo) return SSIP_OK;
   if (pl.stages > 0 && (d->stride != 1 || d->R * d->S > 32)) fallback_regstaged(pl);  // not phase-split here
-  if (pl.stages > 0 && !getenv("SSIP_CONV_FORCE")) {  // the fused epilogue is built for the 128-row tiles only
+  if (pl.stages > 0 && !conv_knobs().force) {  // the fused epilogue is built for the 128-row tiles only
     pl.bm = 128; pl.wmw = 4; pl.wnw = 2; pl.stages = 2;
     pl.bn = (pl.args.Ng % 128 == 0) ? 128 : 64;
     pl.args.tiles_n = ceil_div(pl.args.Ng, pl.bn);

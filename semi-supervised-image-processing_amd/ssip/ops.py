@@ -182,29 +182,36 @@ class ConvGeom:
 # plans depend only on the geometry (and on SSIP_* tuning variables, read at
 # each call by the library): memoised per (geometry, environment) for the host path
 _plan_cache = {}
+# every variable csrc/conv.hip reads that can change a plan query's answer
+# (SSIP_STAGGER changes only the launched kernel's schedule)
+_PLAN_ENV = ("SSIP_HALO", "SSIP_CONV_FORCE", "SSIP_WGRAD_BIG", "SSIP_WGRAD_BLOCKS", "SSIP_BNRELU_GLDS",
+             "SSIP_BNRELU_GLDS_MINM", "SSIP_NO_FWD_DSFUSE")
 
 
 def _plan_env():
-    return tuple(os.environ.get(k) for k in ("SSIP_HALO", "SSIP_CONV_FORCE", "SSIP_WGRAD_BIG"))
+    return tuple(os.environ.get(k) for k in _PLAN_ENV)
 
 
-def conv_fwd_partial_floats(g: ConvGeom) -> int:
-    key = ("pf", g, _plan_env())
+def _plan_query(fn: str, *args, positive: bool = False):
+    """The library's answer to plan query fn(*args), memoised per (arguments,
+    environment); positive: an answer <= 0 raises the library's error."""
+    key = (fn, args, _plan_env())
     v = _plan_cache.get(key)
     if v is None:
-        v = _plan_cache[key] = int(_lib.lib().ssip_conv_fwd_partial_floats(g.desc()))
+        v = getattr(_lib.lib(), fn)(*(a.desc() if isinstance(a, ConvGeom) else _DT[a] if isinstance(a, torch.dtype)
+                                      else a for a in args))
+        if positive and v <= 0:
+            raise RuntimeError(_lib.lib().ssip_last_error().decode())
+        _plan_cache[key] = v
     return v
 
 
+def conv_fwd_partial_floats(g: ConvGeom) -> int:
+    return int(_plan_query("ssip_conv_fwd_partial_floats", g))
+
+
 def conv_fwd_partial_tiles(g: ConvGeom, dtype: torch.dtype) -> int:
-    key = ("pt", g, dtype, _plan_env())
-    t = _plan_cache.get(key)
-    if t is None:
-        t = int(_lib.lib().ssip_conv_fwd_partial_tiles(g.desc(), _DT[dtype]))
-        if t <= 0:
-            raise RuntimeError(_lib.lib().ssip_last_error().decode())
-        _plan_cache[key] = t
-    return t
+    return int(_plan_query("ssip_conv_fwd_partial_tiles", g, dtype, positive=True))
 
 
 def conv_fwd(g: ConvGeom, x: torch.Tensor, w_krsc: torch.Tensor, y: torch.Tensor,
@@ -225,14 +232,7 @@ def conv_fwd(g: ConvGeom, x: torch.Tensor, w_krsc: torch.Tensor, y: torch.Tensor
 
 def conv_fwd_ds_partial_tiles(g: ConvGeom, gds: ConvGeom, dtype: torch.dtype) -> int:
     """BN records per channel the fused forward writes for the downsample."""
-    key = ("pds", g, gds, dtype, _plan_env(), os.environ.get("SSIP_NO_FWD_DSFUSE"))
-    t = _plan_cache.get(key)
-    if t is None:
-        t = int(_lib.lib().ssip_conv_fwd_ds_partial_tiles(g.desc(), gds.desc(), _DT[dtype]))
-        if t <= 0:
-            raise RuntimeError(_lib.lib().ssip_last_error().decode())
-        _plan_cache[key] = t
-    return t
+    return int(_plan_query("ssip_conv_fwd_ds_partial_tiles", g, gds, dtype, positive=True))
 
 
 def conv_fwd_ds(g: ConvGeom, x: torch.Tensor, w_krsc: torch.Tensor, y: torch.Tensor, partial: Optional[torch.Tensor],
@@ -337,11 +337,7 @@ def conv_dgrad_bn(g: ConvGeom, dy: torch.Tensor, w_crsk: torch.Tensor, dx_add: O
 
 def conv_wgrad_workspace_bytes(g: ConvGeom, max_workgroups: int = 0) -> int:
     """Workspace of conv_wgrad(g, ..., max_workgroups) (0: the full-chip grid)."""
-    key = ("ws", g, int(max_workgroups), _plan_env())
-    v = _plan_cache.get(key)
-    if v is None:
-        v = _plan_cache[key] = int(_lib.lib().ssip_conv_wgrad_workspace_bytes_budget(g.desc(), int(max_workgroups)))
-    return v
+    return int(_plan_query("ssip_conv_wgrad_workspace_bytes_budget", g, int(max_workgroups)))
 
 
 def conv_wgrad(g: ConvGeom, dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, accumulate: bool,
@@ -367,11 +363,7 @@ def conv_wgrad(g: ConvGeom, dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor,
 def conv_bnrelu_in_supported(g: ConvGeom, dtype: torch.dtype) -> bool:
     """The conv can take relu(bn(y)) of the layer below as its input, formed in
     its LDS tile (the layer-1 halo geometry; ssip_conv_*_bnrelu_in)."""
-    key = ("bri", g, dtype, _plan_env())
-    v = _plan_cache.get(key)
-    if v is None:
-        v = _plan_cache[key] = bool(_lib.lib().ssip_conv_bnrelu_in_supported(g.desc(), _DT[dtype]))
-    return v
+    return bool(_plan_query("ssip_conv_bnrelu_in_supported", g, dtype))
 
 
 def conv_fwd_bnrelu_in(g: ConvGeom, y_in: torch.Tensor, in_scale: torch.Tensor, in_shift: torch.Tensor,

@@ -1,11 +1,11 @@
 """Layer-1 halo conv lab (GPU box): the 3x3 / stride-1 / 64-channel forward and
 dgrad of ResNet-18 layer 1 (conv_halo_kernel) at batch 256 and 128, timed
-with HIP events, per SSIP_HALO_DIAG ablation (timing only, results wrong):
-0 full, 16 epilogue not deferred (results right), 4 no input-row DMA after the first
-tile, 8 no BN statistics (bits combine).  Speed of light per launch:
-max(FLOPs / 2.5 PF, (x + y bytes) / 8 TB/s).
+with HIP events, then the stem conv and the pool passes behind it.  Speed of
+light per launch: max(FLOPs / 2.5 PF, (x + y bytes) / 8 TB/s).  (The kernels'
+timing ablations of rounds 5-6 are gone; their numbers: profiles/r5_halo_lab.txt,
+profiles/r6_halo_intake.txt.)
 
-usage: python tools/halo_lab.py [--diags 0,1,2,3,4,8,12] [--iters 20]
+usage: python tools/halo_lab.py [--batches 256,128] [--iters 20]
 """
 import argparse
 import os
@@ -21,9 +21,7 @@ from tune_conv import time_fn  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--diags", default="0,16,4,8,12")
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--stem-diags", default="0", help="SSIP_STEM_DIAG values: 1 no stores, 8 no BN statistics")
     ap.add_argument("--batches", default="256,128")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -39,13 +37,10 @@ def main():
         sol = max(g.flops() / 2.5e15, 2 * x.numel() * 2 / 8e12) * 1e6
         print(f"batch {n}: {ops.conv_kernel_name('fwd', g, bf)} / {ops.conv_kernel_name('dgrad', g, bf)}; "
               f"SoL {sol:.1f} us", flush=True)
-        for dg in a.diags.split(","):
-            os.environ["SSIP_HALO_DIAG"] = dg
-            tf = time_fn(lambda: ops.conv_fwd(g, x, w, y, part), a.iters)
-            td = time_fn(lambda: ops.conv_dgrad(g, y, wc, dx), a.iters)
-            print(f"  diag {dg}: fwd {tf:6.1f} us ({sol / tf:.2f} SoL, {g.flops() / tf / 1e6:4.0f} TF/s)"
-                  f"  dgrad {td:6.1f} us ({sol / td:.2f} SoL)", flush=True)
-        os.environ.pop("SSIP_HALO_DIAG", None)
+        tf = time_fn(lambda: ops.conv_fwd(g, x, w, y, part), a.iters)
+        td = time_fn(lambda: ops.conv_dgrad(g, y, wc, dx), a.iters)
+        print(f"  fwd {tf:6.1f} us ({sol / tf:.2f} SoL, {g.flops() / tf / 1e6:4.0f} TF/s)"
+              f"  dgrad {td:6.1f} us ({sol / td:.2f} SoL)", flush=True)
         # the step's other two dgrad forms: + residual gradient, and the fused
         # BN-backward reduction of the BN+ReLU below (mask from its affine)
         add = torch.randn_like(dx)
@@ -63,12 +58,9 @@ def main():
         ws_ = (torch.randn(64, 7, 8, 4, device=dev) * 0.05).to(bf)
         ys = torch.empty(n, 112, 112, 64, device=dev, dtype=bf)
         ssol = max(gs.flops() / 2.5e15, (xs.numel() + ys.numel()) * 2 / 8e12) * 1e6
-        for sd in a.stem_diags.split(","):
-            os.environ["SSIP_STEM_DIAG"] = sd
-            t = time_fn(lambda: ops.conv_fwd(gs, xs, ws_, ys, part), a.iters)
-            print(f"  stem {ops.conv_kernel_name('fwd', gs, bf)} diag {sd}: {t:6.1f} us ({ssol / t:.2f} of SoL "
-                  f"{ssol:.1f} us)", flush=True)
-        os.environ.pop("SSIP_STEM_DIAG", None)
+        t = time_fn(lambda: ops.conv_fwd(gs, xs, ws_, ys, part), a.iters)
+        print(f"  stem {ops.conv_kernel_name('fwd', gs, bf)}: {t:6.1f} us ({ssol / t:.2f} of SoL {ssol:.1f} us)",
+              flush=True)
         sc = torch.rand(64, device=dev) + 0.5
         sh = torch.randn(64, device=dev) * 0.1
         pool = torch.empty(n, 56, 56, 64, device=dev, dtype=bf)

@@ -20,7 +20,8 @@ from tune_conv import shapes, time_fn  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cfg", default="default;128,128,4,2,3;256,128,4,2,2;128,256,2,4,2;256,256,4,2,2;256,256,4,4,2")
+    # the wgrad configurations the library instantiates (csrc/conv.hip SSIP_GLDS_WG)
+    ap.add_argument("--cfg", default="default;128,128,4,2,2;64,128,2,4,2;128,256,2,4,2;256,256,4,2,2")
     ap.add_argument("--budgets", default="0,256")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default="l2.3x3s2,l2.3x3,l3.3x3s2,l3.3x3,l4.3x3s2,l4.3x3")
