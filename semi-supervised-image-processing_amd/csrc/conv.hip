@@ -3055,6 +3055,12 @@ __global__ void __launch_bounds__(768, 1) conv_stem_bwd_wgrad2_kernel(const Stem
 
 // ---------------------------------------------------------------------------
 // host-side planning
+//
+// Every extern "C" entry point has one shape: read the knobs once
+// (conv_knobs), route the call (route_fwd / route_dgrad / route_wgrad: the
+// one place that orders the kernel families), validate pointers and
+// workspace, fill the operands, launch.  The size queries and the name query
+// read the same route objects, so they cannot disagree with a launch.
 // ---------------------------------------------------------------------------
 struct Plan {
   int mode;
@@ -3093,11 +3099,23 @@ static void pick_tile(int M, int Ng, int elem_bytes, Plan& pl) {
   }
 }
 
-static bool glds_has(int mode, bool stem, int bm, int bn, int wm, int wn, int st);
-static int device_cus();
+static int elem_bytes_of(int dtype) { return dtype == SSIP_BF16 ? 2 : 4; }
 
-// The tuning knobs of this file, read from the environment on every call
-// (tests and labs flip them in one process): this file's only environment reads.
+static int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, v = 0;
+    cus = (hipGetDevice(&dev) == hipSuccess &&
+           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+              ? v
+              : 256;
+  }
+  return cus;
+}
+
+// The tuning knobs of this file, read from the environment once per extern "C"
+// call (tests and labs flip them in one process) and handed down: this file's
+// only environment reads.
 // ssip/ops.py keys its plan cache on these names (tests/test_cpu_conv_knobs.py).
 struct ConvKnobs {
   bool halo;           // SSIP_HALO (0: off): the halo / stem kernels where they apply
@@ -3130,6 +3148,86 @@ static ConvKnobs conv_knobs() {
   k.bnrelu_minm = e ? atol(e) : 262144l;
   k.no_fwd_dsfuse = getenv("SSIP_NO_FWD_DSFUSE") != nullptr;
   return k;
+}
+
+// ---- kernel instances: one table and one lookup per implicit-GEMM family
+typedef void (*ConvKernel)(const ConvArgs);
+static const char* const MODE_NAME[3] = {"fwd", "dgrad", "wgrad"};
+
+// LDS-DMA ring kernel configurations (bm, bn, waves_m, waves_n, stages):
+// the ones choose_glds() selects (round 3's wider tuning sets are on the
+// r3-variants branch, with tools/tune_conv.py's lists)
+#define SSIP_GLDS_FD(X, M, F) \
+  X(M, F, 128, 128, 4, 2, 2) X(M, F, 128, 64, 4, 2, 2) X(M, F, 256, 256, 4, 2, 2) X(M, F, 128, 128, 4, 4, 3)
+// (the first two: the full-grid tiles; the other two: the side-stream budget's)
+#define SSIP_GLDS_WG(X, M, F) \
+  X(M, F, 128, 128, 4, 2, 2) X(M, F, 64, 128, 2, 4, 2) X(M, F, 128, 256, 2, 4, 2) X(M, F, 256, 256, 4, 2, 2)
+// the fused BN-backward epilogue (DGRAD) and the folded eval BN epilogue (FWD): the default tiles only
+#define SSIP_GLDS_POST(X, M, F) X(M, F, 128, 128, 4, 2, 2) X(M, F, 128, 64, 4, 2, 2)
+#define SSIP_GLDS_FOLD(X, M, F) SSIP_GLDS_FD(X, M, F)
+#define SSIP_GLDS_STEM(X, M, F) X(M, F, 128, 64, 4, 2, 2)
+// the LDS-DMA ring configurations with the BN+ReLU-in operand transform
+#define SSIP_GLDS_INBN_FD(X, M, F) X(M, F, 128, 128, 4, 2, 2) X(M, F, 128, 64, 4, 2, 2) X(M, F, 256, 256, 4, 2, 2)
+#define SSIP_GLDS_INBN_WG(X, M, F) X(M, F, 128, 128, 4, 2, 2)
+
+enum GldsForm { GLDS_PLAIN, GLDS_STEM, GLDS_POST, GLDS_FOLD, GLDS_INBN };
+// per form: check_launch's name, and the "no <what> kernel for <tile>" of a tile without an instance
+static const struct { const char *check, *what; } GLDS_FORMS[] = {
+    {"conv_glds", "LDS-DMA conv"},          {"conv_glds_stem", "LDS-DMA stem"},    {"conv_glds_bnpost", "fused-BN dgrad"},
+    {"conv_glds_fold", "folded-BN conv"},   {"conv_glds_inbn", "BN+ReLU-in conv"}};
+
+struct GldsRow {
+  int mode, form, bm, bn, wmw, wnw, stages;
+  ConvKernel fn;
+};
+#define SSIP_GLDS_ROW(M, F, BM_, BN_, WM_, WN_, ST_)                                                         \
+  {M, F, BM_, BN_, WM_, WN_, ST_,                                                                            \
+   conv_glds_kernel<M, BM_, BN_, WM_, WN_, ST_, F == GLDS_STEM, F == GLDS_POST, F == GLDS_FOLD, F == GLDS_INBN>},
+static const GldsRow GLDS_TABLE[] = {
+    SSIP_GLDS_FD(SSIP_GLDS_ROW, MODE_FWD, GLDS_PLAIN) SSIP_GLDS_FD(SSIP_GLDS_ROW, MODE_DGRAD, GLDS_PLAIN)
+    SSIP_GLDS_WG(SSIP_GLDS_ROW, MODE_WGRAD, GLDS_PLAIN) SSIP_GLDS_STEM(SSIP_GLDS_ROW, MODE_FWD, GLDS_STEM)
+    SSIP_GLDS_POST(SSIP_GLDS_ROW, MODE_DGRAD, GLDS_POST) SSIP_GLDS_FOLD(SSIP_GLDS_ROW, MODE_FWD, GLDS_FOLD)
+    SSIP_GLDS_INBN_FD(SSIP_GLDS_ROW, MODE_FWD, GLDS_INBN) SSIP_GLDS_INBN_WG(SSIP_GLDS_ROW, MODE_WGRAD, GLDS_INBN)};
+#undef SSIP_GLDS_ROW
+
+static const GldsRow* glds_find(int mode, int form, int bm, int bn, int wmw, int wnw, int stages) {
+  for (const GldsRow& r : GLDS_TABLE)
+    if (r.mode == mode && r.form == form && bm == r.bm && bn == r.bn && wmw == r.wmw && wnw == r.wnw &&
+        stages == r.stages)
+      return &r;
+  return nullptr;
+}
+
+// Register-staged kernel instances: 4 waves over 128 (WGRAD: also 64) rows
+// for both dtypes, 8 waves over 256 rows for a bf16 FWD / DGRAD (pick_tile);
+// conv1: the C = 4 stem (no DGRAD)
+#define SSIP_GEMM_128(X, M, T, C1) X(M, T, 128, 128, 2, 2, C1) X(M, T, 128, 64, 2, 2, C1)
+#define SSIP_GEMM_256(X, M, C1) X(M, __bf16, 256, 128, 4, 2, C1) X(M, __bf16, 256, 64, 4, 2, C1)
+#define SSIP_GEMM_WG(X, T, C1) SSIP_GEMM_128(X, MODE_WGRAD, T, C1) X(MODE_WGRAD, T, 64, 128, 2, 2, C1)
+
+struct GemmRow {
+  int mode, elem_bytes, bm, bn, wmw, wnw;
+  bool conv1;
+  ConvKernel fn;
+};
+#define SSIP_GEMM_ROW(M, T, BM_, BN_, WM_, WN_, C1) \
+  {M, (int)sizeof(T), BM_, BN_, WM_, WN_, C1, conv_gemm_kernel<M, T, BM_, BN_, WM_, WN_, C1>},
+static const GemmRow GEMM_TABLE[] = {
+    SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_FWD, __bf16, false) SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_FWD, __bf16, true)
+    SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_FWD, float, false) SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_FWD, float, true)
+    SSIP_GEMM_256(SSIP_GEMM_ROW, MODE_FWD, false) SSIP_GEMM_256(SSIP_GEMM_ROW, MODE_FWD, true)
+    SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_DGRAD, __bf16, false) SSIP_GEMM_128(SSIP_GEMM_ROW, MODE_DGRAD, float, false)
+    SSIP_GEMM_256(SSIP_GEMM_ROW, MODE_DGRAD, false)
+    SSIP_GEMM_WG(SSIP_GEMM_ROW, __bf16, false) SSIP_GEMM_WG(SSIP_GEMM_ROW, __bf16, true)
+    SSIP_GEMM_WG(SSIP_GEMM_ROW, float, false) SSIP_GEMM_WG(SSIP_GEMM_ROW, float, true)};
+#undef SSIP_GEMM_ROW
+
+static const GemmRow* gemm_find(int mode, int elem_bytes, int bm, int bn, int wmw, int wnw, bool conv1) {
+  for (const GemmRow& r : GEMM_TABLE)
+    if (r.mode == mode && r.elem_bytes == elem_bytes && bm == r.bm && bn == r.bn && wmw == r.wmw && wnw == r.wnw &&
+        conv1 == r.conv1)
+      return &r;
+  return nullptr;
 }
 
 // A wgrad with a budget (on the side stream) takes 8-wave 256x256 tiles, and
@@ -3181,15 +3279,18 @@ static void choose_glds(int mode, const ConvArgs& a, Plan& pl) {
 static int apply_force(const ConvKnobs& k, int mode, int elem_bytes, Plan& pl) {
   const char* e = k.force;
   if (!e || !e[0]) return SSIP_OK;
-  const char want = mode == MODE_FWD ? 'f' : mode == MODE_DGRAD ? 'd' : 'w';
-  if (e[0] != want || (pl.conv1 && !pl.stem_glds)) return SSIP_OK;
+  if (e[0] != MODE_NAME[mode][0] || (pl.conv1 && !pl.stem_glds)) return SSIP_OK;
   int bm, bn, wm, wn, st;
   SSIP_REQUIRE(sscanf(e + 1, ",%d,%d,%d,%d,%d", &bm, &bn, &wm, &wn, &st) == 5, SSIP_ERR_ARG,
                "bad SSIP_CONV_FORCE '%s'", e);
   if (st > 0) {
-    SSIP_REQUIRE(elem_bytes == 2 && glds_has(mode, pl.conv1, bm, bn, wm, wn, st), SSIP_ERR_ARG,
+    const int form = (mode == MODE_FWD && pl.conv1) ? GLDS_STEM : GLDS_PLAIN;
+    SSIP_REQUIRE(elem_bytes == 2 && glds_find(mode, form, bm, bn, wm, wn, st), SSIP_ERR_ARG,
                  "SSIP_CONV_FORCE: no LDS-DMA kernel %s", e);
   } else {
+    // not a gemm_find: this accepts a 64x64 wgrad tile, which GEMM_TABLE does not
+    // hold (the launch then reports "no wgrad kernel for tile 64x64"); every
+    // other answer is the table's
     const bool ok = mode == MODE_WGRAD ? (wm == 2 && wn == 2 && (bm == 128 || bm == 64))
                                        : ((bm == 256 && wm == 4 && wn == 2 && elem_bytes == 2) ||
                                           (bm == 128 && wm == 2 && wn == 2));
@@ -3211,10 +3312,9 @@ static int stagger_for(const ConvKnobs& k, int mode, const Plan& pl) {
   return (k.stagger >> mode) & 1;
 }
 
-static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl, int wg_budget = 0,
-                     bool allow_big = true) {
+static int plan_conv(const ConvKnobs& k, int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl,
+                     int wg_budget = 0, bool allow_big = true) {
   SSIP_REQUIRE(desc_ok(d), SSIP_ERR_ARG, "bad conv descriptor");
-  const ConvKnobs k = conv_knobs();
   pl.mode = mode;
   pl.conv1 = (d->C == 4);
   // the padded stem stores S = 8 columns for a real 7-wide filter
@@ -3331,162 +3431,43 @@ static int plan_conv(int mode, const ssip_conv_desc* d, int elem_bytes, Plan& pl
   return SSIP_OK;
 }
 
-// LDS-DMA ring kernel configurations (bm, bn, waves_m, waves_n, stages):
-// the ones choose_glds() selects (round 3's wider tuning sets are on the
-// r3-variants branch, with tools/tune_conv.py's lists)
-#define SSIP_GLDS_FD(X) X(128, 128, 4, 2, 2) X(128, 64, 4, 2, 2) X(256, 256, 4, 2, 2) X(128, 128, 4, 4, 3)
-// (the first two: the full-grid tiles; the other two: the side-stream budget's)
-#define SSIP_GLDS_WG(X) X(128, 128, 4, 2, 2) X(64, 128, 2, 4, 2) X(128, 256, 2, 4, 2) X(256, 256, 4, 2, 2)
-#define SSIP_GLDS_POST(X) X(128, 128, 4, 2, 2) X(128, 64, 4, 2, 2)
-#define SSIP_GLDS_FOLD(X) SSIP_GLDS_FD(X)
-#define SSIP_GLDS_STEM(X) X(128, 64, 4, 2, 2)
-
-static bool glds_has(int mode, bool stem, int bm, int bn, int wm, int wn, int st) {
-#define SSIP_GLDS_EQ(BM_, BN_, WM_, WN_, ST_) \
-  if (bm == BM_ && bn == BN_ && wm == WM_ && wn == WN_ && st == ST_) return true;
-  if (mode == MODE_WGRAD) {
-    SSIP_GLDS_WG(SSIP_GLDS_EQ)
-  } else if (mode == MODE_FWD && stem) {
-    SSIP_GLDS_STEM(SSIP_GLDS_EQ)
-  } else {
-    SSIP_GLDS_FD(SSIP_GLDS_EQ)
-  }
-#undef SSIP_GLDS_EQ
-  return false;
+// the ring kernel's form follows from the operands the entry point has set
+static int glds_form(const Plan& pl) {
+  const ConvArgs& a = pl.args;
+  if (pl.mode != MODE_DGRAD && a.in_scale != nullptr) return GLDS_INBN;
+  if (pl.mode == MODE_DGRAD && a.pmean != nullptr) return GLDS_POST;  // fused BN-backward epilogue
+  if (pl.mode == MODE_FWD && a.bias != nullptr) return GLDS_FOLD;     // folded eval BN epilogue
+  if (pl.mode == MODE_FWD && pl.conv1) return GLDS_STEM;
+  return GLDS_PLAIN;
 }
 
-// the LDS-DMA ring configurations with the BN+ReLU-in operand transform
-#define SSIP_GLDS_INBN_FD(X) X(128, 128, 4, 2, 2) X(128, 64, 4, 2, 2) X(256, 256, 4, 2, 2)
-#define SSIP_GLDS_INBN_WG(X) X(128, 128, 4, 2, 2)
-
-template <int MODE>
 static int launch_glds(const Plan& pl, hipStream_t st) {
-  if constexpr (MODE != MODE_DGRAD) {
-    if (pl.args.in_scale != nullptr) {
-#define SSIP_GLDS_GOI(BM_, BN_, WM_, WN_, ST_)                                                                \
-  if (pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_) {                   \
-    SSIP_KLAUNCH((conv_glds_kernel<MODE, BM_, BN_, WM_, WN_, ST_, false, false, false, true>), pl.grid,      \
-                 dim3(64 * WM_ * WN_), 0, st, pl.args);                                                       \
-    return ::ssip::check_launch("conv_glds_inbn");                                                            \
-  }
-      if constexpr (MODE == MODE_WGRAD) {
-        SSIP_GLDS_INBN_WG(SSIP_GLDS_GOI)
-      } else {
-        SSIP_GLDS_INBN_FD(SSIP_GLDS_GOI)
-      }
-#undef SSIP_GLDS_GOI
-      ::ssip::set_error("no BN+ReLU-in conv kernel for %dx%d/%dx%d/%d", pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
-      return SSIP_ERR_ARG;
-    }
-  }
-#define SSIP_GLDS_GO(BM_, BN_, WM_, WN_, ST_)                                                                 \
-  if (pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_) {                   \
-    SSIP_KLAUNCH((conv_glds_kernel<MODE, BM_, BN_, WM_, WN_, ST_>), pl.grid, dim3(64 * WM_ * WN_), 0,   \
-                       st, pl.args);                                                                          \
-    return ::ssip::check_launch("conv_glds");                                                                 \
-  }
-  if constexpr (MODE == MODE_WGRAD) {
-    SSIP_GLDS_WG(SSIP_GLDS_GO)
-  } else {
-    if constexpr (MODE == MODE_DGRAD) {
-      if (pl.args.pmean != nullptr) {  // fused BN-backward epilogue: default tiles only
-#define SSIP_GLDS_GOP(BM_, BN_, WM_, WN_, ST_)                                                                \
-  if (pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_) {                   \
-    SSIP_KLAUNCH((conv_glds_kernel<MODE, BM_, BN_, WM_, WN_, ST_, false, true>), pl.grid,               \
-                       dim3(64 * WM_ * WN_), 0, st, pl.args);                                                 \
-    return ::ssip::check_launch("conv_glds_bnpost");                                                          \
-  }
-        SSIP_GLDS_POST(SSIP_GLDS_GOP)
-#undef SSIP_GLDS_GOP
-        ::ssip::set_error("no fused-BN dgrad kernel for %dx%d/%dx%d/%d", pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
-        return SSIP_ERR_ARG;
-      }
-    }
-    if constexpr (MODE == MODE_FWD) {
-      if (pl.args.bias != nullptr) {  // folded eval BN epilogue: the default tiles only
-#define SSIP_GLDS_GOF(BM_, BN_, WM_, WN_, ST_)                                                                \
-  if (pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_) {                   \
-    SSIP_KLAUNCH((conv_glds_kernel<MODE, BM_, BN_, WM_, WN_, ST_, false, false, true>), pl.grid,        \
-                       dim3(64 * WM_ * WN_), 0, st, pl.args);                                                 \
-    return ::ssip::check_launch("conv_glds_fold");                                                            \
-  }
-        SSIP_GLDS_FOLD(SSIP_GLDS_GOF)
-#undef SSIP_GLDS_GOF
-        ::ssip::set_error("no folded-BN conv kernel for %dx%d/%dx%d/%d", pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
-        return SSIP_ERR_ARG;
-      }
-      if (pl.conv1) {
-#define SSIP_GLDS_GO4(BM_, BN_, WM_, WN_, ST_)                                                                \
-  if (pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_) {                   \
-    SSIP_KLAUNCH((conv_glds_kernel<MODE, BM_, BN_, WM_, WN_, ST_, true>), pl.grid, dim3(64 * WM_ * WN_), \
-                       0, st, pl.args);                                                                       \
-    return ::ssip::check_launch("conv_glds_stem");                                                            \
-  }
-        SSIP_GLDS_STEM(SSIP_GLDS_GO4)
-#undef SSIP_GLDS_GO4
-        ::ssip::set_error("no LDS-DMA stem kernel for %dx%d/%dx%d/%d", pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
-        return SSIP_ERR_ARG;
-      }
-    }
-    SSIP_GLDS_FD(SSIP_GLDS_GO)
-  }
-#undef SSIP_GLDS_GO
-  ::ssip::set_error("no LDS-DMA conv kernel for %dx%d/%dx%d/%d", pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
-  return SSIP_ERR_ARG;
+  const int form = glds_form(pl);
+  const GldsRow* r = glds_find(pl.mode, form, pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages);
+  SSIP_REQUIRE(r != nullptr, SSIP_ERR_ARG, "no %s kernel for %dx%d/%dx%d/%d", GLDS_FORMS[form].what, pl.bm, pl.bn,
+               pl.wmw, pl.wnw, pl.stages);
+  SSIP_KLAUNCH(r->fn, pl.grid, dim3(64 * r->wmw * r->wnw), 0, st, pl.args);
+  return ::ssip::check_launch(GLDS_FORMS[form].check);
 }
 
-template <int MODE, typename T>
-static int launch_conv(const Plan& pl, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
-    if (pl.stages > 0) return launch_glds<MODE>(pl, st);
-  }
-#define SSIP_LAUNCH(BM_, BN_, WM_, WN_, C1_)                                                                  \
-  {                                                                                                           \
-    SSIP_KLAUNCH((conv_gemm_kernel<MODE, T, BM_, BN_, WM_, WN_, C1_>), pl.grid, dim3(64 * WM_ * WN_), 0, \
-                       st, pl.args);                                                                          \
-  }
-  const bool c1 = pl.conv1;
-  if constexpr (MODE == MODE_WGRAD) {
-    if (pl.bm == 128 && pl.bn == 128) {
-      if (c1) SSIP_LAUNCH(128, 128, 2, 2, true) else SSIP_LAUNCH(128, 128, 2, 2, false)
-    } else if (pl.bm == 128 && pl.bn == 64) {
-      if (c1) SSIP_LAUNCH(128, 64, 2, 2, true) else SSIP_LAUNCH(128, 64, 2, 2, false)
-    } else if (pl.bm == 64 && pl.bn == 128) {
-      if (c1) SSIP_LAUNCH(64, 128, 2, 2, true) else SSIP_LAUNCH(64, 128, 2, 2, false)
-    } else {
-      ::ssip::set_error("no wgrad kernel for tile %dx%d", pl.bm, pl.bn);
-      return SSIP_ERR_ARG;
-    }
-  } else if constexpr (MODE == MODE_FWD) {
-    if (sizeof(T) == 2 && pl.bm == 256 && pl.bn == 128) {
-      if constexpr (sizeof(T) == 2) { if (c1) SSIP_LAUNCH(256, 128, 4, 2, true) else SSIP_LAUNCH(256, 128, 4, 2, false) }
-    } else if (sizeof(T) == 2 && pl.bm == 256 && pl.bn == 64) {
-      if constexpr (sizeof(T) == 2) { if (c1) SSIP_LAUNCH(256, 64, 4, 2, true) else SSIP_LAUNCH(256, 64, 4, 2, false) }
-    } else if (pl.bm == 128 && pl.bn == 128) {
-      if (c1) SSIP_LAUNCH(128, 128, 2, 2, true) else SSIP_LAUNCH(128, 128, 2, 2, false)
-    } else if (pl.bm == 128 && pl.bn == 64) {
-      if (c1) SSIP_LAUNCH(128, 64, 2, 2, true) else SSIP_LAUNCH(128, 64, 2, 2, false)
-    } else {
-      ::ssip::set_error("no fwd kernel for tile %dx%d", pl.bm, pl.bn);
-      return SSIP_ERR_ARG;
-    }
-  } else {
-    if (sizeof(T) == 2 && pl.bm == 256 && pl.bn == 128) {
-      if constexpr (sizeof(T) == 2) SSIP_LAUNCH(256, 128, 4, 2, false)
-    } else if (sizeof(T) == 2 && pl.bm == 256 && pl.bn == 64) {
-      if constexpr (sizeof(T) == 2) SSIP_LAUNCH(256, 64, 4, 2, false)
-    } else if (pl.bm == 128 && pl.bn == 128) SSIP_LAUNCH(128, 128, 2, 2, false)
-    else if (pl.bm == 128 && pl.bn == 64) SSIP_LAUNCH(128, 64, 2, 2, false)
-    else {
-      ::ssip::set_error("no dgrad kernel for tile %dx%d", pl.bm, pl.bn);
-      return SSIP_ERR_ARG;
-    }
-  }
-#undef SSIP_LAUNCH
+static int launch_conv(const Plan& pl, int dtype, hipStream_t st) {
+  SSIP_REQUIRE(dtype == SSIP_F32 || dtype == SSIP_BF16, SSIP_ERR_ARG, "unsupported dtype %d", dtype);
+  if (dtype == SSIP_BF16 && pl.stages > 0) return launch_glds(pl, st);
+  const GemmRow* r = gemm_find(pl.mode, elem_bytes_of(dtype), pl.bm, pl.bn, pl.wmw, pl.wnw, pl.conv1);
+  SSIP_REQUIRE(r != nullptr, SSIP_ERR_ARG, "no %s kernel for tile %dx%d", MODE_NAME[pl.mode], pl.bm, pl.bn);
+  SSIP_KLAUNCH(r->fn, pl.grid, dim3(64 * r->wmw * r->wnw), 0, st, pl.args);
   return ::ssip::check_launch("conv_gemm");
 }
 
-static int elem_bytes_of(int dtype) { return dtype == SSIP_BF16 ? 2 : 4; }
+// Operand pointers and buffer-descriptor byte sizes of the implicit-GEMM
+// kernels: FWD x and w_krsc, DGRAD dy and w_crsk, WGRAD dy and x
+static void set_operands(ConvArgs& a, const ssip_conv_desc* d, int mode, const void* A, const void* B) {
+  const long x_bytes = (long)d->N * d->H * d->W * d->C * 2, dy_bytes = (long)d->N * d->P * d->Q * d->K * 2;
+  const long w_bytes = (long)d->K * d->R * d->S * d->C * 2;
+  a.A = A; a.B = B;
+  a.a_bytes = (uint32_t)(mode == MODE_FWD ? x_bytes : dy_bytes);
+  a.b_bytes = (uint32_t)(mode == MODE_WGRAD ? x_bytes : w_bytes);
+}
 
 // Register-staged kernel for a FWD/DGRAD GEMM view the LDS-DMA kernel does not
 // address: the strided DGRAD without its phase split, filters of > 32 taps.
@@ -3546,20 +3527,8 @@ struct HaloPlan {
   int TR, tiles, units, G, cols;
 };
 
-static int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-              ? v
-              : 256;
-  }
-  return cus;
-}
-
-static bool halo_plan(int mode, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  if (!conv_knobs().halo_for(mode == MODE_FWD ? 'f' : 'd')) return false;
+static bool halo_plan(const ConvKnobs& k, int mode, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
+  if (!k.halo_for(MODE_NAME[mode][0])) return false;
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 ||
       d->P != d->H || d->Q != d->W)
     return false;
@@ -3585,8 +3554,8 @@ static bool halo_plan(int mode, const ssip_conv_desc* d, int dtype, HaloPlan& hp
 }
 
 // ---- stem path (conv_stem_halo_kernel): the pre-padded 7x7 / stride 2 stem
-static bool stem_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  if (!conv_knobs().halo_for('f')) return false;
+static bool stem_plan(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
+  if (!k.halo_for('f')) return false;
   if (dtype != SSIP_BF16 || !desc_ok(d) || d->C != 4 || d->R != 7 || d->S != 8 || d->stride != 2 || d->pad != 0 ||
       d->K % 64 != 0 || d->Q > STEM_QP || d->P % STEM_TR != 0 || d->W % 2 != 0 ||
       STEM_XROWS * d->W * 8 > STEM_XBUF || d->H < 2 * (d->P - 1) + 7)
@@ -3601,6 +3570,191 @@ static bool stem_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
   return true;
 }
 
+// ---- halo WGRAD (conv_halo_wgrad_kernel): 3x3 / stride 1 / pad 1, C = K = 64, bf16
+static bool halo_wg_plan(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
+  if (!k.halo_for('w')) return false;
+  if (dtype != SSIP_BF16 || !desc_ok(d) || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 ||
+      d->P != d->H || d->Q != d->W || d->C != 64 || d->K != 64)
+    return false;
+  const int Wp = d->W + 2;
+  if (256 + 2 * Wp + 2 > HWG_XBUF / 128) return false;  // shifted reads stay inside the input image
+  int TR = 0;
+  for (int tr = std::min(d->H, 256 / Wp); tr >= 1; --tr)
+    if (d->H % tr == 0 && (tr + 2) * Wp <= HWG_XBUF / 128) {
+      TR = tr;
+      break;
+    }
+  if (TR == 0 || TR * d->W < 128) return false;
+  if ((long)d->N * d->H * d->W * 64 * 2 >= (1l << 31)) return false;
+  hp.TR = TR;
+  hp.cols = 576;  // slab columns: 3 x 3 x 64
+  hp.tiles = d->N * d->H / TR;
+  hp.units = hp.tiles;
+  hp.G = std::min(hp.tiles, device_cus());
+  return true;
+}
+
+// ---- stem WGRAD (conv_stem_wgrad_kernel)
+static bool stem_wg_plan(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
+  if (!k.halo_for('w')) return false;
+  if (!stem_plan(k, d, dtype, hp) || d->K != 64) return false;  // same geometry as the forward's kernel
+  hp.cols = 224;  // slab columns: 7 x 8 x 4
+  hp.G = std::min(hp.tiles, device_cus());
+  hp.units = hp.tiles;
+  return true;
+}
+
+// ---- routes: what one call runs
+enum RouteKind {
+  ROUTE_NONE,        // no kernel takes this descriptor (the route function's return value says why)
+  ROUTE_HALO,        // conv_halo_kernel (FWD / DGRAD): hp
+  ROUTE_STEM,        // conv_stem_halo_kernel (FWD): hp
+  ROUTE_GLDS,        // conv_glds_kernel: pl
+  ROUTE_REGSTAGED,   // conv_gemm_kernel: pl
+  ROUTE_HALO_WGRAD,  // conv_halo_wgrad_kernel + slab reduce: hp
+  ROUTE_STEM_WGRAD   // conv_stem_wgrad_kernel / conv_stem_bwd_wgrad2_kernel + slab reduce: hp
+};
+struct ConvRoute {
+  int kind = ROUTE_NONE;
+  Plan pl;      // the implicit-GEMM plan (for a WGRAD also beside a persistent kind: ssip_conv_wgrad_budget)
+  HaloPlan hp;  // a persistent kernel's grid
+  bool persistent_fwd() const { return kind == ROUTE_HALO || kind == ROUTE_STEM; }
+  bool persistent_wgrad() const { return kind == ROUTE_HALO_WGRAD || kind == ROUTE_STEM_WGRAD; }
+};
+
+static int implicit_kind(const Plan& pl) { return pl.stages > 0 ? ROUTE_GLDS : ROUTE_REGSTAGED; }
+
+// The route functions return plan_conv's verdict on the descriptor, which a
+// launch returns before anything else.  The kind is set wherever a kernel's
+// own test takes the geometry: the stem kernels' does not compare P with H,
+// so on such a descriptor the queries answer for them and the launch fails.
+
+// FWD: the halo kernel, the stem kernel, else the implicit GEMM
+static int route_fwd(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, ConvRoute& r) {
+  const int rc = plan_conv(k, MODE_FWD, d, elem_bytes_of(dtype), r.pl);
+  if (halo_plan(k, MODE_FWD, d, dtype, r.hp)) {
+    r.kind = ROUTE_HALO;
+  } else if (stem_plan(k, d, dtype, r.hp)) {
+    r.kind = ROUTE_STEM;
+  } else if (rc == SSIP_OK) {
+    if (r.pl.stages > 0 && !r.pl.conv1 && d->R * d->S > 32) fallback_regstaged(r.pl);
+    r.kind = implicit_kind(r.pl);
+  }
+  return rc;
+}
+
+// DGRAD: the halo kernel, else the implicit GEMM, stride 2 split by phase.
+// bn_fused (ssip_conv_dgrad_bn's epilogue): no phase split, and the ring
+// kernel at its 128-row tiles, the only ones the epilogue is built for
+// (SSIP_CONV_FORCE for the pass aside).
+static int route_dgrad(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, ConvRoute& r, bool bn_fused = false) {
+  Plan& pl = r.pl;
+  if (int rc = plan_conv(k, MODE_DGRAD, d, elem_bytes_of(dtype), pl)) return rc;
+  if (halo_plan(k, MODE_DGRAD, d, dtype, r.hp)) {
+    r.kind = ROUTE_HALO;
+    return SSIP_OK;
+  }
+  if (!bn_fused) phase_split(pl, d);
+  if (pl.stages > 0 && ((d->stride != 1 && !pl.args.phased) || d->R * d->S > 32)) fallback_regstaged(pl);
+  if (bn_fused && pl.stages > 0 && !k.force) {
+    pl.bm = 128; pl.wmw = 4; pl.wnw = 2; pl.stages = 2;
+    pl.bn = (pl.args.Ng % 128 == 0) ? 128 : 64;
+    pl.args.tiles_n = ceil_div(pl.args.Ng, pl.bn);
+    pl.grid = dim3(ceil_div(pl.args.M, pl.bm) * pl.args.tiles_n, 1, 1);
+  }
+  SSIP_REQUIRE(!bn_fused || pl.bm >= 128, SSIP_ERR_ARG, "ssip_conv_dgrad_bn: partial sizing assumes >= 128-row tiles");
+  r.kind = implicit_kind(pl);
+  return SSIP_OK;
+}
+
+// WGRAD under a workgroup budget (0: none): the stem kernel, the halo kernel
+// (persistent: a budget means fewer workgroups, more tiles each), else the
+// split-K implicit GEMM
+static int route_wgrad(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, int budget, ConvRoute& r) {
+  const int rc = plan_conv(k, MODE_WGRAD, d, elem_bytes_of(dtype), r.pl, budget);
+  if (stem_wg_plan(k, d, dtype, r.hp)) r.kind = ROUTE_STEM_WGRAD;
+  else if (halo_wg_plan(k, d, dtype, r.hp)) r.kind = ROUTE_HALO_WGRAD;
+  else if (rc == SSIP_OK) r.kind = implicit_kind(r.pl);
+  if (r.persistent_wgrad() && budget > 0) r.hp.G = std::min(r.hp.G, budget);
+  return rc;
+}
+
+// BN records per channel the route's kernel writes: one per (workgroup, wave
+// row) of a persistent kernel, one per row tile of the implicit GEMM; -1: no route
+static int route_records(const ConvRoute& r) {
+  if (r.kind == ROUTE_NONE) return -1;
+  return r.persistent_fwd() ? r.hp.G * HALO_WMW : ceil_div(r.pl.args.M, r.pl.bm);
+}
+
+// fp32 slab bytes of a wgrad: one M x Ng slab per split / per persistent workgroup
+static int64_t implicit_slab_bytes(const Plan& pl) { return (int64_t)pl.splits * pl.args.M * pl.args.Ng * 4; }
+static int64_t persistent_slab_bytes(const HaloPlan& hp) { return (int64_t)hp.G * 64 * hp.cols * 4; }
+
+// A 3x3 / pad-1 / stride-s conv and its block's 1x1 / pad-0 / stride-s
+// downsample over the same input and output grid: one LDS-DMA launch when the
+// conv takes a 2- or 3-stage ring kernel (else false: two launches).
+static bool fwd_ds_plan(const ConvKnobs& k, const ssip_conv_desc* d, const ssip_conv_desc* dds, int dtype,
+                        ConvRoute& r) {
+  if (dtype != SSIP_BF16 || !desc_ok(d) || !desc_ok(dds) || k.no_fwd_dsfuse) return false;
+  if (d->R != 3 || d->S != 3 || d->pad != 1 || dds->R != 1 || dds->S != 1 || dds->pad != 0 ||
+      dds->stride != d->stride || dds->N != d->N || dds->H != d->H || dds->W != d->W || dds->C != d->C ||
+      dds->K != d->K || dds->P != d->P || dds->Q != d->Q || d->C % 64 != 0)
+    return false;
+  return route_fwd(k, d, dtype, r) == SSIP_OK && r.kind == ROUTE_GLDS && !r.pl.conv1 &&
+         (r.pl.stages == 2 || r.pl.stages == 3);
+}
+
+// ssip_conv_*_bnrelu_in beyond the layer-1 halo geometry: the LDS-DMA ring
+// kernels with the INBN operand transform, for bf16 stride-1 convs with
+// 64 <= C <= GLDS_INBN_C input channels -- 1x1 / pad 0 (the ResNet-50
+// bottleneck's conv3 over relu(bn2(y2))) with SSIP_BNRELU_GLDS bit 0, 3x3 /
+// pad 1 with bit 1.  The transform keeps padding taps, rows past the grid
+// and split tails zero.
+// SSIP_BNRELU_GLDS: bit 0 the 1x1 / stride-1 form (default on: config 5,
+// 60.23 vs 60.60 ms/step with the forward's z_out, profiles/r6_bnrelu_in_glds_lab.txt),
+// bit 1 the 3x3 form (off: slower in both steps)
+static bool glds_inbn_plan(const ConvKnobs& k, int mode, const ssip_conv_desc* d, int dtype, Plan& pl,
+                           int budget = 0) {
+  if (dtype != SSIP_BF16 || !desc_ok(d) || d->stride != 1 || d->C % 64 || d->C > GLDS_INBN_C || d->K % 64)
+    return false;
+  // the 1x1 form pays where the apply pass it removes is large: per launch it
+  // wins at ResNet-50 layers 1-2 (>= 262,144 rows) and loses at layers 3-4,
+  // where the conv is short and the in-ring transform is not hidden
+  // (profiles/r6_bnrelu_in_glds_lab.txt); SSIP_BNRELU_GLDS_MINM overrides
+  if (d->R == 1 && (long)d->N * d->H * d->W < k.bnrelu_minm) return false;
+  const bool g1 = d->R == 1 && d->S == 1 && d->pad == 0 && (k.bnrelu_glds & 1);
+  const bool g3 = d->R == 3 && d->S == 3 && d->pad == 1 && (k.bnrelu_glds & 2);
+  if (!g1 && !g3) return false;
+  ConvRoute rf;
+  const int rc_fwd = route_fwd(k, d, dtype, rf);
+  if (rf.kind == ROUTE_HALO) return false;  // the halo geometry has its own BN+ReLU-in kernels
+  if (mode == MODE_FWD) {
+    if (rc_fwd) return false;
+    pl = rf.pl;
+  } else if (plan_conv(k, mode, d, 2, pl, budget, false) != SSIP_OK) {
+    // (the wide budget tiles of SSIP_WGRAD_BIG have no INBN form: the budget's plain tiles)
+    return false;
+  }
+  if (pl.conv1 || pl.stages != 2) return false;
+  return glds_find(mode, GLDS_INBN, pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages) != nullptr;
+}
+
+// BN+ReLU-in support: forward and wgrad both on the halo kernels (rf, rw), or
+// both on an INBN ring kernel (rf.pl: the forward's plan)
+static bool bnrelu_in_routes(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, ConvRoute& rf, ConvRoute& rw) {
+  route_fwd(k, d, dtype, rf);
+  route_wgrad(k, d, dtype, 0, rw);
+  if (rf.kind == ROUTE_HALO && rw.kind == ROUTE_HALO_WGRAD) return true;
+  return glds_inbn_plan(k, MODE_FWD, d, dtype, rf.pl) && glds_inbn_plan(k, MODE_WGRAD, d, dtype, rw.pl);
+}
+
+// the fused stem backward (conv_stem_bwd_wgrad2_kernel): the stem wgrad's geometry at Q = 112
+static bool stem_bwd_route(const ConvKnobs& k, const ssip_conv_desc* d, int dtype, ConvRoute& r) {
+  route_wgrad(k, d, dtype, 0, r);
+  return r.kind == ROUTE_STEM_WGRAD && d->Q * 2 == 224 && d->P % 2 == 0;
+}
+
+// ---- launches
 static int launch_stem_halo(const ssip_conv_desc* d, const HaloPlan& hp, const void* X, const void* Wt, void* out,
                             float* partial, hipStream_t st) {
   StemArgs s;
@@ -3617,44 +3771,23 @@ static int launch_stem_halo(const ssip_conv_desc* d, const HaloPlan& hp, const v
   return ::ssip::check_launch("conv_stem_halo");
 }
 
-// ---- halo WGRAD (conv_halo_wgrad_kernel): 3x3 / stride 1 / pad 1, C = K = 64, bf16
-static bool halo_wg_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  if (!conv_knobs().halo_for('w')) return false;
-  if (dtype != SSIP_BF16 || !desc_ok(d) || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 ||
-      d->P != d->H || d->Q != d->W || d->C != 64 || d->K != 64)
-    return false;
-  const int Wp = d->W + 2;
-  if (256 + 2 * Wp + 2 > HWG_XBUF / 128) return false;  // shifted reads stay inside the input image
-  int TR = 0;
-  for (int tr = std::min(d->H, 256 / Wp); tr >= 1; --tr)
-    if (d->H % tr == 0 && (tr + 2) * Wp <= HWG_XBUF / 128) {
-      TR = tr;
-      break;
-    }
-  if (TR == 0 || TR * d->W < 128) return false;
-  if ((long)d->N * d->H * d->W * 64 * 2 >= (1l << 31)) return false;
-  hp.TR = TR;
-  hp.cols = 576;
-  hp.tiles = d->N * d->H / TR;
-  hp.units = hp.tiles;
-  hp.G = std::min(hp.tiles, device_cus());
-  return true;
-}
-
-// ---- stem WGRAD (conv_stem_wgrad_kernel)
-static bool stem_wg_plan(const ssip_conv_desc* d, int dtype, HaloPlan& hp) {
-  if (!conv_knobs().halo_for('w')) return false;
-  if (!stem_plan(d, dtype, hp) || d->K != 64) return false;  // same geometry as the forward's kernel
-  hp.G = std::min(hp.tiles, device_cus());
-  hp.units = hp.tiles;
-  return true;
-}
-
 struct HaloBnPost {
   const void* y;
   const uint8_t* bits;
   const float *mean, *invstd, *mscale, *mshift;
 };
+
+// 8 waves of 64x32 (16 waves of 32x32 were ~10 % faster in isolation but 3 %
+// slower in the step, where the side streams' kernels run beside them; 4
+// waves of 64x64 slower still: r3-variants branch)
+typedef void (*HaloKernel)(const HaloArgs);
+static HaloKernel halo_kernel(bool inbn, int bnpost, bool bias, bool add) {
+  if (inbn) return conv_halo_kernel<4, 2, false, 0, false, true>;  // FWD over relu(bn(y)) of the layer below, formed in LDS
+  if (bnpost == 1) return conv_halo_kernel<4, 2, false, 1>;        // DGRAD + BN-backward reduction
+  if (bnpost == 2) return conv_halo_kernel<4, 2, false, 2>;        // ... with a residual gradient or mask bits
+  if (bias) return add ? conv_halo_kernel<4, 2, true, 0, true> : conv_halo_kernel<4, 2, true>;  // folded eval BN epilogue
+  return add ? conv_halo_kernel<4, 2, false, 0, true> : conv_halo_kernel<4, 2>;
+}
 
 static int launch_halo(int mode, const ssip_conv_desc* d, const HaloPlan& hp, const void* X, const void* Wt,
                        void* out, const void* add, float* partial, hipStream_t st, const float* bias = nullptr,
@@ -3681,36 +3814,34 @@ static int launch_halo(int mode, const ssip_conv_desc* d, const HaloPlan& hp, co
   h.N = d->N; h.H = d->H; h.W = d->W; h.Ncols = hp.cols;
   h.TR = hp.TR; h.tiles = hp.tiles; h.units = hp.units;
   h.flip = mode == MODE_DGRAD ? 1 : 0;
-  // 8 waves of 64x32 (16 waves of 32x32 were ~10 % faster in isolation but 3 %
-  // slower in the step, where the side streams' kernels run beside them; 4
-  // waves of 64x64 slower still: r3-variants branch)
   h.in_scale = in_scale;
   h.in_shift = in_shift;
   h.zout = static_cast<__bf16*>(zout);
-  if (in_scale != nullptr)  // FWD over relu(bn(y)) of the layer below, formed in LDS
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, false, true>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (bp != nullptr && add == nullptr && bp->bits == nullptr)  // DGRAD + BN-backward reduction
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 1>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (bp != nullptr)
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 2>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (bias != nullptr && add != nullptr)  // folded eval BN epilogue
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, true, 0, true>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (bias != nullptr)
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, true>), dim3(hp.G), dim3(512), 0, st, h);
-  else if (add != nullptr)
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2, false, 0, true>), dim3(hp.G), dim3(512), 0, st, h);
-  else
-    SSIP_KLAUNCH((conv_halo_kernel<4, 2>), dim3(hp.G), dim3(512), 0, st, h);
+  const int bnpost = bp == nullptr ? 0 : (add == nullptr && bp->bits == nullptr) ? 1 : 2;
+  SSIP_KLAUNCH(halo_kernel(in_scale != nullptr, bnpost, bias != nullptr, add != nullptr), dim3(hp.G), dim3(512), 0,
+               st, h);
   return ::ssip::check_launch("conv_halo");
+}
+
+// The fixed-order reduce of `splits` fp32 slabs [K][Ng] (Ng = R * S * C stored
+// columns: C % 32 == 0, or the stem's 7 x 8 x 4) into dw [K][c_real][R][s_real]
+static int launch_slab_reduce(const void* slab, int splits, int K, int Ng, int c_real, int R, int s_real, int C,
+                              int S, float* dw_kcrs, int accumulate, hipStream_t st) {
+  const long total4 = (long)K * Ng / 4;
+  int lg = 0;  // split groups: double while splits allow and the grid stays within ~1024 workgroups
+  while (lg < 6 && (2 << lg) <= splits && ((total4 << (lg + 1)) + 255) / 256 <= 1024) ++lg;
+  const long blocks = (total4 + (256 >> lg) - 1) / (256 >> lg);
+  SSIP_KLAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)slab, splits, K, Ng,
+               c_real, R, s_real, C, S, dw_kcrs, accumulate, lg);
+  return ::ssip::check_launch("wgrad_reduce");
 }
 
 // layer-1 WGRAD on conv_halo_wgrad_kernel + its slab reduce (in_scale: the
 // input is y of the BN+ReLU below, transformed in LDS)
-static int launch_halo_wgrad(const ssip_conv_desc* d, HaloPlan hp, const void* dy, const void* x, float* dw_kcrs,
-                             int c_real, int s_real, int accumulate, void* workspace, int64_t workspace_bytes,
-                             int max_workgroups, hipStream_t st, const float* in_scale, const float* in_shift) {
-  if (max_workgroups > 0) hp.G = std::min(hp.G, max_workgroups);  // persistent: fewer CUs, more tiles each
-  const int64_t hneed = (int64_t)hp.G * 64 * 576 * 4;
+static int launch_halo_wgrad(const ssip_conv_desc* d, const HaloPlan& hp, const void* dy, const void* x,
+                             float* dw_kcrs, int c_real, int s_real, int accumulate, void* workspace,
+                             int64_t workspace_bytes, hipStream_t st, const float* in_scale, const float* in_shift) {
+  const int64_t hneed = persistent_slab_bytes(hp);
   SSIP_REQUIRE(workspace_bytes >= hneed, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
                (long long)workspace_bytes, (long long)hneed);
   HaloWgArgs h;
@@ -3721,19 +3852,56 @@ static int launch_halo_wgrad(const ssip_conv_desc* d, HaloPlan hp, const void* d
   h.N = d->N; h.H = d->H; h.W = d->W; h.TR = hp.TR; h.tiles = hp.tiles;
   h.in_scale = in_scale;
   h.in_shift = in_shift;
-  if (in_scale != nullptr)
-    SSIP_KLAUNCH(conv_halo_wgrad_kernel<true>, dim3(hp.G), dim3(512), 0, st, h);
-  else
-    SSIP_KLAUNCH(conv_halo_wgrad_kernel<false>, dim3(hp.G), dim3(512), 0, st, h);
-  int rc = ::ssip::check_launch("conv_halo_wgrad");
-  if (rc) return rc;
-  const long total4 = 64L * 576 / 4;
-  int lg = 0;
-  while (lg < 6 && (2 << lg) <= hp.G && ((total4 << (lg + 1)) + 255) / 256 <= 1024) ++lg;
-  const long blocks = (total4 + (256 >> lg) - 1) / (256 >> lg);
-  SSIP_KLAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace, hp.G, 64, 576,
-               c_real, 3, s_real, 64, 3, dw_kcrs, accumulate, lg);
-  return ::ssip::check_launch("wgrad_reduce");
+  SSIP_KLAUNCH(in_scale != nullptr ? conv_halo_wgrad_kernel<true> : conv_halo_wgrad_kernel<false>, dim3(hp.G),
+               dim3(512), 0, st, h);
+  if (int rc = ::ssip::check_launch("conv_halo_wgrad")) return rc;
+  return launch_slab_reduce(workspace, hp.G, 64, hp.cols, c_real, 3, s_real, 64, 3, dw_kcrs, accumulate, st);
+}
+
+// the stem's WGRAD on conv_stem_wgrad_kernel + its slab reduce
+static int launch_stem_wgrad(const ssip_conv_desc* d, const HaloPlan& hp, const void* dy, const void* x,
+                             float* dw_kcrs, int c_real, int s_real, int accumulate, void* workspace,
+                             int64_t workspace_bytes, hipStream_t st) {
+  const int64_t sneed = persistent_slab_bytes(hp);
+  SSIP_REQUIRE(workspace_bytes >= sneed, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
+               (long long)workspace_bytes, (long long)sneed);
+  StemWgArgs h;
+  h.X = static_cast<const __bf16*>(x);
+  h.DY = static_cast<const __bf16*>(dy);
+  h.slab = static_cast<float*>(workspace);
+  h.x_bytes = (uint32_t)((long)d->N * d->H * d->W * 8);
+  h.dy_bytes = (uint32_t)((long)d->N * d->P * d->Q * 64 * 2);
+  h.N = d->N; h.H = d->H; h.W = d->W; h.P = d->P; h.Q = d->Q; h.tiles = hp.tiles;
+  SSIP_KLAUNCH(conv_stem_wgrad_kernel, dim3(hp.G), dim3(512), 0, st, h);
+  if (int rc = ::ssip::check_launch("conv_stem_wgrad")) return rc;
+  return launch_slab_reduce(workspace, hp.G, 64, hp.cols, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate, st);
+}
+
+// the split-K implicit-GEMM wgrad of a planned conv + its fixed-order slab
+// reduce (ssip_conv_wgrad_budget; ssip_conv_wgrad_bnrelu_in with in_scale set)
+static int wgrad_implicit(Plan& pl, const ssip_conv_desc* d, int dtype, const void* dy, const void* x,
+                          float* dw_kcrs, int c_real, int s_real, int accumulate, void* workspace, hipStream_t st) {
+  ConvArgs& g = pl.args;
+  set_operands(g, d, MODE_WGRAD, dy, x);
+  g.out = workspace;
+  const int PQ = d->P * d->Q, BKr = 64;  // LDS-DMA k-step rows (bf16)
+  const int dn = BKr / PQ, rem = BKr % PQ;
+  g.wg_dn = dn;
+  g.wg_dp = rem / d->Q;
+  g.wg_dq = rem % d->Q;
+  g.wg_k0 = (dn * d->H * d->W + g.wg_dp * d->stride * d->W + g.wg_dq * d->stride) * d->C * 2;
+  g.wg_e1 = (d->stride * d->W - d->Q * d->stride) * d->C * 2;
+  g.wg_e2 = (d->H * d->W - d->P * d->stride * d->W) * d->C * 2;
+  if (int rc = launch_conv(pl, dtype, st)) return rc;
+  const int RS = d->R * d->S;
+  if (c_real == d->C && s_real == d->S && d->C % 64 == 0 && RS <= WGR_T_MAXRS && g.Ng == RS * d->C &&
+      pl.splits <= 32 && (long)d->K * (d->C / 64) >= 256 && (reinterpret_cast<uintptr_t>(dw_kcrs) & 15) == 0) {
+    SSIP_KLAUNCH(wgrad_reduce_t_kernel, dim3((unsigned)(d->K * (d->C / 64))), dim3(256), 0, st,
+                 (const float*)workspace, pl.splits, d->K, g.Ng, d->C, RS, dw_kcrs, accumulate);
+    return ::ssip::check_launch("wgrad_reduce_t");
+  }
+  return launch_slab_reduce(workspace, pl.splits, d->K, g.Ng, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate,
+                            st);
 }
 
 }  // namespace
@@ -3741,15 +3909,14 @@ static int launch_halo_wgrad(const ssip_conv_desc* d, HaloPlan hp, const void* d
 extern "C" {
 
 int64_t ssip_conv_fwd_partial_floats(const ssip_conv_desc* d) {
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r32, r16;
+  const int rc32 = route_fwd(k, d, SSIP_F32, r32), rc16 = route_fwd(k, d, SSIP_BF16, r16);
+  if (rc32 && rc16) return -1;
   // the partial-buffer size must not depend on dtype: size for the smaller (128-row) tiles
-  Plan pl;
-  if (plan_conv(MODE_FWD, d, 4, pl) != SSIP_OK) {
-    if (plan_conv(MODE_FWD, d, 2, pl) != SSIP_OK) return -1;
-  }
-  int64_t n = (int64_t)ceil_div(pl.args.M, 128) * d->K * 3;
-  HaloPlan hp;  // one record per (channel, workgroup) on the halo path
-  if (halo_plan(MODE_FWD, d, SSIP_BF16, hp)) n = std::max(n, (int64_t)hp.G * HALO_WMW * d->K * 3);
-  if (stem_plan(d, SSIP_BF16, hp)) n = std::max(n, (int64_t)hp.G * HALO_WMW * d->K * 3);
+  int64_t n = (int64_t)ceil_div((rc32 ? r16 : r32).pl.args.M, 128) * d->K * 3;
+  // one record per (channel, workgroup, wave row) where bf16 takes a persistent kernel
+  if (r16.persistent_fwd()) n = std::max(n, (int64_t)route_records(r16) * d->K * 3);
   // + the scratch of ssip_bn_finalize's split pass (the most records any
   // plan writes bounds the splits; the scratch starts behind the records)
   return n + fin_scratch_floats(d->K, n / (3 * d->K), 3);
@@ -3757,109 +3924,84 @@ int64_t ssip_conv_fwd_partial_floats(const ssip_conv_desc* d) {
 
 int ssip_conv_fwd(const ssip_conv_desc* d, int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial,
                   void* stream) {
-  Plan pl;
-  int rc = plan_conv(MODE_FWD, d, elem_bytes_of(dtype), pl);
-  if (rc) return rc;
-  if (pl.stages > 0 && !pl.conv1 && d->R * d->S > 32) fallback_regstaged(pl);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_fwd(k, d, dtype, r)) return rc;
   SSIP_REQUIRE(x && w_krsc && y, SSIP_ERR_ARG, "ssip_conv_fwd: null pointer");
-  HaloPlan hp;
-  if (halo_plan(MODE_FWD, d, dtype, hp))
-    return launch_halo(MODE_FWD, d, hp, x, w_krsc, y, nullptr, bn_partial, (hipStream_t)stream);
-  if (stem_plan(d, dtype, hp)) return launch_stem_halo(d, hp, x, w_krsc, y, bn_partial, (hipStream_t)stream);
-  pl.args.A = x; pl.args.B = w_krsc; pl.args.out = y; pl.args.partial = bn_partial;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->H * d->W * d->C * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
-  SSIP_DISPATCH_DTYPE(dtype, T, return launch_conv<MODE_FWD, T>(pl, (hipStream_t)stream));
+  if (r.kind == ROUTE_HALO)
+    return launch_halo(MODE_FWD, d, r.hp, x, w_krsc, y, nullptr, bn_partial, (hipStream_t)stream);
+  if (r.kind == ROUTE_STEM) return launch_stem_halo(d, r.hp, x, w_krsc, y, bn_partial, (hipStream_t)stream);
+  set_operands(r.pl.args, d, MODE_FWD, x, w_krsc);
+  r.pl.args.out = y; r.pl.args.partial = bn_partial;
+  return launch_conv(r.pl, dtype, (hipStream_t)stream);
 }
 
-// A 3x3 / pad-1 / stride-s conv and its block's 1x1 / pad-0 / stride-s
-// downsample over the same input and output grid: one LDS-DMA launch when the
-// conv takes a 2- or 3-stage ring kernel (else false: two launches).
-static bool fwd_ds_plan(const ssip_conv_desc* d, const ssip_conv_desc* dds, int dtype, Plan& pl) {
-  if (dtype != SSIP_BF16 || !desc_ok(d) || !desc_ok(dds) || conv_knobs().no_fwd_dsfuse) return false;
-  if (d->R != 3 || d->S != 3 || d->pad != 1 || dds->R != 1 || dds->S != 1 || dds->pad != 0 ||
-      dds->stride != d->stride || dds->N != d->N || dds->H != d->H || dds->W != d->W || dds->C != d->C ||
-      dds->K != d->K || dds->P != d->P || dds->Q != d->Q || d->C % 64 != 0)
-    return false;
-  HaloPlan hp;
-  if (halo_plan(MODE_FWD, d, dtype, hp) || stem_plan(d, dtype, hp)) return false;
-  if (plan_conv(MODE_FWD, d, 2, pl) != SSIP_OK || pl.conv1) return false;
-  return pl.stages == 2 || pl.stages == 3;
+int ssip_conv_fwd_partial_tiles(const ssip_conv_desc* d, int dtype) {
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  route_fwd(k, d, dtype, r);
+  return route_records(r);
 }
 
 int ssip_conv_fwd_ds_partial_tiles(const ssip_conv_desc* d, const ssip_conv_desc* dds, int dtype) {
-  Plan pl;
-  if (fwd_ds_plan(d, dds, dtype, pl)) return ceil_div(pl.args.M, pl.bm);
-  return ssip_conv_fwd_partial_tiles(dds, dtype);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r, rds;
+  if (fwd_ds_plan(k, d, dds, dtype, r)) return route_records(r);
+  route_fwd(k, dds, dtype, rds);  // two launches: the downsample's own
+  return route_records(rds);
 }
 
 int ssip_conv_fwd_ds(const ssip_conv_desc* d, const ssip_conv_desc* dds, int dtype, const void* x, const void* w_krsc,
                      void* y, float* bn_partial, const void* wds_kc, void* y_ds, float* bn_partial_ds, void* stream) {
   SSIP_REQUIRE(x && w_krsc && y && wds_kc && y_ds, SSIP_ERR_ARG, "ssip_conv_fwd_ds: null pointer");
-  Plan pl;
-  if (!fwd_ds_plan(d, dds, dtype, pl)) {  // two launches
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (!fwd_ds_plan(k, d, dds, dtype, r)) {  // two launches
     int rc = ssip_conv_fwd(d, dtype, x, w_krsc, y, bn_partial, stream);
     if (rc) return rc;
     return ssip_conv_fwd(dds, dtype, x, wds_kc, y_ds, bn_partial_ds, stream);
   }
   SSIP_REQUIRE((bn_partial == nullptr) == (bn_partial_ds == nullptr), SSIP_ERR_ARG,
                "ssip_conv_fwd_ds: both or neither BN partial buffers");
+  Plan& pl = r.pl;
   ConvArgs& a = pl.args;
-  a.A = x; a.B = w_krsc; a.out = y; a.partial = bn_partial;
-  a.a_bytes = (uint32_t)((long)d->N * d->H * d->W * d->C * 2);
-  a.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
+  set_operands(a, d, MODE_FWD, x, w_krsc);
+  a.out = y; a.partial = bn_partial;
   const int T1 = (int)pl.grid.x;
   a.fwd_tiles1 = T1;
   a.Bds = wds_kc; a.out_ds = y_ds; a.partial_ds = bn_partial_ds;
   a.bds_bytes = (uint32_t)((long)d->K * d->C * 2);
   a.stat_tiles_m = ceil_div(a.M, pl.bm);
   pl.grid = dim3(2 * T1, 1, 1);
-  return launch_conv<MODE_FWD, __bf16>(pl, (hipStream_t)stream);
-}
-
-int ssip_conv_fwd_partial_tiles(const ssip_conv_desc* d, int dtype) {
-  HaloPlan hp;
-  if (halo_plan(MODE_FWD, d, dtype, hp)) return hp.G * HALO_WMW;
-  if (stem_plan(d, dtype, hp)) return hp.G * HALO_WMW;
-  Plan pl;
-  if (plan_conv(MODE_FWD, d, elem_bytes_of(dtype), pl) != SSIP_OK) return -1;
-  if (pl.stages > 0 && !pl.conv1 && d->R * d->S > 32) fallback_regstaged(pl);
-  return ceil_div(pl.args.M, pl.bm);
+  return launch_conv(pl, dtype, (hipStream_t)stream);
 }
 
 int ssip_conv_fwd_bias(const ssip_conv_desc* d, int dtype, const void* x, const void* w_krsc, const float* bias,
                        const void* residual, int relu, void* y, void* stream) {
-  Plan pl;
-  int rc = plan_conv(MODE_FWD, d, elem_bytes_of(dtype), pl);
-  if (rc) return rc;
-  SSIP_REQUIRE(!pl.conv1, SSIP_ERR_ARG, "ssip_conv_fwd_bias: not for the C = 4 stem");
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_fwd(k, d, dtype, r)) return rc;
+  SSIP_REQUIRE(!r.pl.conv1, SSIP_ERR_ARG, "ssip_conv_fwd_bias: not for the C = 4 stem");
   SSIP_REQUIRE(x && w_krsc && bias && y, SSIP_ERR_ARG, "ssip_conv_fwd_bias: null pointer");
-  if (pl.stages > 0 && d->R * d->S > 32) fallback_regstaged(pl);
-  HaloPlan hp;
-  if (halo_plan(MODE_FWD, d, dtype, hp))
-    return launch_halo(MODE_FWD, d, hp, x, w_krsc, y, residual, nullptr, (hipStream_t)stream, bias, relu ? 1 : 0);
-  pl.args.A = x; pl.args.B = w_krsc; pl.args.out = y; pl.args.partial = nullptr;
-  pl.args.add = residual; pl.args.bias = bias; pl.args.relu = relu ? 1 : 0;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->H * d->W * d->C * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
-  SSIP_DISPATCH_DTYPE(dtype, T, return launch_conv<MODE_FWD, T>(pl, (hipStream_t)stream));
+  if (r.kind == ROUTE_HALO)
+    return launch_halo(MODE_FWD, d, r.hp, x, w_krsc, y, residual, nullptr, (hipStream_t)stream, bias, relu ? 1 : 0);
+  set_operands(r.pl.args, d, MODE_FWD, x, w_krsc);
+  r.pl.args.out = y; r.pl.args.partial = nullptr;
+  r.pl.args.add = residual; r.pl.args.bias = bias; r.pl.args.relu = relu ? 1 : 0;
+  return launch_conv(r.pl, dtype, (hipStream_t)stream);
 }
 
 int ssip_conv_dgrad(const ssip_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dx,
                     const void* dx_add, void* stream) {
-  Plan pl;
-  int rc = plan_conv(MODE_DGRAD, d, elem_bytes_of(dtype), pl);
-  if (rc) return rc;
-  phase_split(pl, d);
-  if (pl.stages > 0 && ((d->stride != 1 && !pl.args.phased) || d->R * d->S > 32)) fallback_regstaged(pl);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_dgrad(k, d, dtype, r)) return rc;
   SSIP_REQUIRE(dy && w_crsk && dx, SSIP_ERR_ARG, "ssip_conv_dgrad: null pointer");
-  HaloPlan hp;
-  if (halo_plan(MODE_DGRAD, d, dtype, hp))
-    return launch_halo(MODE_DGRAD, d, hp, dy, w_crsk, dx, dx_add, nullptr, (hipStream_t)stream);
-  pl.args.A = dy; pl.args.B = w_crsk; pl.args.out = dx; pl.args.add = dx_add;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->P * d->Q * d->K * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
-  SSIP_DISPATCH_DTYPE(dtype, T, return launch_conv<MODE_DGRAD, T>(pl, (hipStream_t)stream));
+  if (r.kind == ROUTE_HALO)
+    return launch_halo(MODE_DGRAD, d, r.hp, dy, w_crsk, dx, dx_add, nullptr, (hipStream_t)stream);
+  set_operands(r.pl.args, d, MODE_DGRAD, dy, w_crsk);
+  r.pl.args.out = dx; r.pl.args.add = dx_add;
+  return launch_conv(r.pl, dtype, (hipStream_t)stream);
 }
 
 int ssip_conv_dgrad_ds(const ssip_conv_desc* d, int dtype, const void* dy, const void* w_crsk, const void* dy_ds,
@@ -3870,20 +4012,18 @@ int ssip_conv_dgrad_ds(const ssip_conv_desc* d, int dtype, const void* dy, const
                "ssip_conv_dgrad_ds: the 1x1 downsample's output grid must equal the conv's (H, W divisible by stride)");
   ssip_conv_desc dd = *d;  // the block's 1x1 / stride downsample: same input, same output grid
   dd.R = 1; dd.S = 1; dd.pad = 0;
-  Plan pl;
-  int rc = plan_conv(MODE_DGRAD, d, elem_bytes_of(dtype), pl);
-  if (rc) return rc;
-  phase_split(pl, d);
-  const bool fuse = pl.stages > 0 && pl.args.phased && d->R == 3 && d->S == 3 && d->pad == 1 && d->stride == 2;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_dgrad(k, d, dtype, r)) return rc;
+  const bool fuse = r.kind == ROUTE_GLDS && r.pl.args.phased && d->R == 3 && d->S == 3 && d->pad == 1 && d->stride == 2;
   if (!fuse) {  // two passes: the conv's dgrad, then the downsample's accumulated in place
-    rc = ssip_conv_dgrad(d, dtype, dy, w_crsk, dx, nullptr, stream);
+    int rc = ssip_conv_dgrad(d, dtype, dy, w_crsk, dx, nullptr, stream);
     if (rc) return rc;
     return ssip_conv_dgrad(&dd, dtype, dy_ds, wds_ck, dx, dx, stream);
   }
-  ConvArgs& a = pl.args;
-  a.A = dy; a.B = w_crsk; a.out = dx; a.add = nullptr;
-  a.a_bytes = (uint32_t)((long)d->N * d->P * d->Q * d->K * 2);
-  a.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
+  ConvArgs& a = r.pl.args;
+  set_operands(a, d, MODE_DGRAD, dy, w_crsk);
+  a.out = dx; a.add = nullptr;
   a.A2 = dy_ds; a.B2 = wds_ck;
   a.a2_bytes = a.a_bytes;
   a.b2_bytes = (uint32_t)((long)d->K * d->C * 2);
@@ -3893,130 +4033,69 @@ int ssip_conv_dgrad_ds(const ssip_conv_desc* d, int dtype, const void* dy, const
   a.ds_from = a.phase[0].ksteps;
   a.phase[0].ksteps += d->K / 64;
   set_phase_order(a);
-  return launch_conv<MODE_DGRAD, __bf16>(pl, (hipStream_t)stream);
+  return launch_conv(r.pl, dtype, (hipStream_t)stream);
 }
 
 int64_t ssip_conv_dgrad_bn_partial_floats(const ssip_conv_desc* d) {
-  Plan pl;
-  if (plan_conv(MODE_DGRAD, d, 4, pl) != SSIP_OK) {
-    if (plan_conv(MODE_DGRAD, d, 2, pl) != SSIP_OK) return -1;
-  }
-  long tiles = ceil_div(pl.args.M, 128);  // the LDS-DMA / register-staged paths: >= 128-row tiles
-  HaloPlan hp;
-  if (halo_plan(MODE_DGRAD, d, SSIP_BF16, hp)) tiles = std::max<long>(tiles, (long)hp.G * HALO_WMW);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r32, r16;
+  const int rc32 = route_dgrad(k, d, SSIP_F32, r32, true), rc16 = route_dgrad(k, d, SSIP_BF16, r16, true);
+  if (rc32 && rc16) return -1;
+  long tiles = ceil_div((rc32 ? r16 : r32).pl.args.M, 128);  // the LDS-DMA / register-staged paths: >= 128-row tiles
+  if (r16.kind == ROUTE_HALO) tiles = std::max<long>(tiles, route_records(r16));
   return tiles * d->C * 2 + fin_scratch_floats(d->C, tiles, 2);  // + ssip_bn_bwd_from_partials' split scratch
 }
 
-static int wgrad_implicit(Plan& pl, const ssip_conv_desc* d, int dtype, const void* dy, const void* x,
-                          float* dw_kcrs, int c_real, int s_real, int accumulate, void* workspace, hipStream_t st);
-
-// ssip_conv_*_bnrelu_in beyond the layer-1 halo geometry: the LDS-DMA ring
-// kernels with the INBN operand transform, for bf16 stride-1 convs with
-// 64 <= C <= GLDS_INBN_C input channels -- 1x1 / pad 0 (the ResNet-50
-// bottleneck's conv3 over relu(bn2(y2))) with SSIP_BNRELU_GLDS bit 0, 3x3 /
-// pad 1 with bit 1.  The transform keeps padding taps, rows past the grid
-// and split tails zero.
-// SSIP_BNRELU_GLDS: bit 0 the 1x1 / stride-1 form (default on: config 5,
-// 60.23 vs 60.60 ms/step with the forward's z_out, profiles/r6_bnrelu_in_glds_lab.txt),
-// bit 1 the 3x3 form (off: slower in both steps)
-static bool glds_inbn_plan(int mode, const ssip_conv_desc* d, int dtype, Plan& pl, int budget = 0) {
-  if (dtype != SSIP_BF16 || !desc_ok(d) || d->stride != 1 || d->C % 64 || d->C > GLDS_INBN_C || d->K % 64)
-    return false;
-  const ConvKnobs k = conv_knobs();
-  // the 1x1 form pays where the apply pass it removes is large: per launch it
-  // wins at ResNet-50 layers 1-2 (>= 262,144 rows) and loses at layers 3-4,
-  // where the conv is short and the in-ring transform is not hidden
-  // (profiles/r6_bnrelu_in_glds_lab.txt); SSIP_BNRELU_GLDS_MINM overrides
-  if (d->R == 1 && (long)d->N * d->H * d->W < k.bnrelu_minm) return false;
-  const bool g1 = d->R == 1 && d->S == 1 && d->pad == 0 && (k.bnrelu_glds & 1);
-  const bool g3 = d->R == 3 && d->S == 3 && d->pad == 1 && (k.bnrelu_glds & 2);
-  if (!g1 && !g3) return false;
-  HaloPlan hp;
-  if (halo_plan(MODE_FWD, d, dtype, hp)) return false;
-  // (the wide budget tiles of SSIP_WGRAD_BIG have no INBN form: the budget's plain tiles)
-  if (plan_conv(mode, d, 2, pl, budget, false) != SSIP_OK || pl.conv1 || pl.stages != 2) return false;
-  bool ok = false;
-#define SSIP_GLDS_INBN_EQ(BM_, BN_, WM_, WN_, ST_) \
-  ok |= pl.bm == BM_ && pl.bn == BN_ && pl.wmw == WM_ && pl.wnw == WN_ && pl.stages == ST_;
-  if (mode == MODE_WGRAD) {
-    SSIP_GLDS_INBN_WG(SSIP_GLDS_INBN_EQ)
-  } else {
-    SSIP_GLDS_INBN_FD(SSIP_GLDS_INBN_EQ)
-  }
-#undef SSIP_GLDS_INBN_EQ
-  return ok;
-}
-
-// the kernel ssip_conv_dgrad_bn runs: the halo kernel where it applies, else
-// the implicit-GEMM kernels at their 128-row tiles (no phase split)
-static int dgrad_bn_plan(const ssip_conv_desc* d, int dtype, Plan& pl, HaloPlan& hp, bool& halo) {
-  int rc = plan_conv(MODE_DGRAD, d, elem_bytes_of(dtype), pl);
-  if (rc) return rc;
-  halo = halo_plan(MODE_DGRAD, d, dtype, hp);
-  if (halo) return SSIP_OK;
-  if (pl.stages > 0 && (d->stride != 1 || d->R * d->S > 32)) fallback_regstaged(pl);  // not phase-split here
-  if (pl.stages > 0 && !conv_knobs().force) {  // the fused epilogue is built for the 128-row tiles only
-    pl.bm = 128; pl.wmw = 4; pl.wnw = 2; pl.stages = 2;
-    pl.bn = (pl.args.Ng % 128 == 0) ? 128 : 64;
-    pl.args.tiles_n = ceil_div(pl.args.Ng, pl.bn);
-    pl.grid = dim3(ceil_div(pl.args.M, pl.bm) * pl.args.tiles_n, 1, 1);
-  }
-  SSIP_REQUIRE(pl.bm >= 128, SSIP_ERR_ARG, "ssip_conv_dgrad_bn: partial sizing assumes >= 128-row tiles");
-  return SSIP_OK;
-}
-
 int ssip_conv_dgrad_bn_partial_tiles(const ssip_conv_desc* d, int dtype) {
-  Plan pl;
-  HaloPlan hp;
-  bool halo = false;
-  if (dgrad_bn_plan(d, dtype, pl, hp, halo) != SSIP_OK) return -1;
-  return halo ? hp.G * HALO_WMW : ceil_div(pl.args.M, pl.bm);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  route_dgrad(k, d, dtype, r, true);
+  return route_records(r);
 }
 
 int ssip_conv_dgrad_bn(const ssip_conv_desc* d, int dtype, const void* dy, const void* w_crsk, const void* dx_add,
                        const void* zmask, const uint8_t* mask_bits, const float* mscale, const float* mshift,
                        const void* y, const float* mean, const float* invstd, void* dpre, float* partial,
                        void* stream) {
-  Plan pl;
-  HaloPlan hp;
-  bool halo = false;
-  int rc = dgrad_bn_plan(d, dtype, pl, hp, halo);
-  if (rc) return rc;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_dgrad(k, d, dtype, r, true)) return rc;
   SSIP_REQUIRE(dy && w_crsk && y && mean && invstd && dpre && partial, SSIP_ERR_ARG,
                "ssip_conv_dgrad_bn: null pointer");
   SSIP_REQUIRE(zmask || mask_bits || (mscale && mshift), SSIP_ERR_ARG,
                "ssip_conv_dgrad_bn: one ReLU-mask source (zmask, mask_bits or mscale+mshift) is required");
   SSIP_REQUIRE(d->C % 8 == 0, SSIP_ERR_ARG, "ssip_conv_dgrad_bn: C must be a multiple of 8");
-  if (halo) {
+  if (r.kind == ROUTE_HALO) {
     SSIP_REQUIRE(!zmask || mask_bits || (mscale && mshift), SSIP_ERR_ARG,
                  "ssip_conv_dgrad_bn: the halo kernel takes mask bits or the BN affine, not z");
     HaloBnPost bp;
     bp.y = y; bp.bits = mask_bits; bp.mean = mean; bp.invstd = invstd;
     bp.mscale = mask_bits ? nullptr : mscale; bp.mshift = mask_bits ? nullptr : mshift;
-    return launch_halo(MODE_DGRAD, d, hp, dy, w_crsk, dpre, dx_add, partial, (hipStream_t)stream, nullptr, 0, &bp);
+    return launch_halo(MODE_DGRAD, d, r.hp, dy, w_crsk, dpre, dx_add, partial, (hipStream_t)stream, nullptr, 0, &bp);
   }
-  pl.args.A = dy; pl.args.B = w_crsk; pl.args.out = dpre; pl.args.add = dx_add;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->P * d->Q * d->K * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
-  pl.args.pmask = zmask; pl.args.pbits = zmask ? nullptr : mask_bits;
-  pl.args.pmscale = (zmask || mask_bits) ? nullptr : mscale; pl.args.pmshift = (zmask || mask_bits) ? nullptr : mshift;
-  pl.args.py = y; pl.args.pmean = mean; pl.args.pinvstd = invstd; pl.args.partial = partial;
-  SSIP_DISPATCH_DTYPE(dtype, T, return launch_conv<MODE_DGRAD, T>(pl, (hipStream_t)stream));
+  ConvArgs& a = r.pl.args;
+  set_operands(a, d, MODE_DGRAD, dy, w_crsk);
+  a.out = dpre; a.add = dx_add;
+  a.pmask = zmask; a.pbits = zmask ? nullptr : mask_bits;
+  a.pmscale = (zmask || mask_bits) ? nullptr : mscale; a.pmshift = (zmask || mask_bits) ? nullptr : mshift;
+  a.py = y; a.pmean = mean; a.pinvstd = invstd; a.partial = partial;
+  return launch_conv(r.pl, dtype, (hipStream_t)stream);
 }
 
 int64_t ssip_conv_wgrad_workspace_bytes_budget(const ssip_conv_desc* d, int max_workgroups) {
-  // max over dtypes so one workspace serves both
-  Plan p2, p4;
-  int64_t b = -1;
   if (max_workgroups < 0) return -1;
-  if (plan_conv(MODE_WGRAD, d, 2, p2, max_workgroups) == SSIP_OK) b = (int64_t)p2.splits * p2.args.M * p2.args.Ng * 4;
-  if (max_workgroups > 0 && plan_conv(MODE_WGRAD, d, 2, p2, max_workgroups, false) == SSIP_OK)  // the INBN form's plan
-    b = std::max<int64_t>(b, (int64_t)p2.splits * p2.args.M * p2.args.Ng * 4);
-  if (plan_conv(MODE_WGRAD, d, 4, p4, max_workgroups) == SSIP_OK)
-    b = std::max<int64_t>(b, (int64_t)p4.splits * p4.args.M * p4.args.Ng * 4);
-  HaloPlan hp;
-  if (b >= 0 && halo_wg_plan(d, SSIP_BF16, hp)) b = std::max<int64_t>(b, (int64_t)hp.G * 64 * 576 * 4);
-  if (b >= 0 && stem_wg_plan(d, SSIP_BF16, hp)) b = std::max<int64_t>(b, (int64_t)hp.G * 64 * 224 * 4);
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  int64_t b = -1;
+  // max over dtypes so one workspace serves both, and over the INBN form's plan (glds_inbn_plan: no wide tiles)
+  const struct { int elem_bytes; bool big; } plans[] = {{2, true}, {2, false}, {4, true}};
+  for (const auto& p : plans)
+    if ((p.big || max_workgroups > 0) &&
+        plan_conv(k, MODE_WGRAD, d, p.elem_bytes, r.pl, max_workgroups, p.big) == SSIP_OK)
+      b = std::max(b, implicit_slab_bytes(r.pl));
+  // a persistent kernel at its full grid: a budget only shrinks it
+  if (b >= 0) route_wgrad(k, d, SSIP_BF16, 0, r);
+  if (r.persistent_wgrad()) b = std::max(b, persistent_slab_bytes(r.hp));
   return b;
 }
 
@@ -4032,100 +4111,42 @@ int ssip_conv_wgrad_budget(const ssip_conv_desc* d, int dtype, const void* dy, c
                            int c_real, int s_real, int accumulate, void* workspace, int64_t workspace_bytes,
                            int max_workgroups, void* stream) {
   SSIP_REQUIRE(max_workgroups >= 0, SSIP_ERR_ARG, "ssip_conv_wgrad_budget: negative budget");
-  Plan pl;
-  int rc = plan_conv(MODE_WGRAD, d, elem_bytes_of(dtype), pl, max_workgroups);
-  if (rc) return rc;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  if (int rc = route_wgrad(k, d, dtype, max_workgroups, r)) return rc;
   SSIP_REQUIRE(dy && x && dw_kcrs && workspace, SSIP_ERR_ARG, "ssip_conv_wgrad: null pointer");
-  const int64_t need = (int64_t)pl.splits * pl.args.M * pl.args.Ng * 4;
+  // (the implicit plan's need, whichever kernel runs: the workspace query returns the maximum)
+  const int64_t need = implicit_slab_bytes(r.pl);
   SSIP_REQUIRE(workspace_bytes >= need, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
                (long long)workspace_bytes, (long long)need);
   SSIP_REQUIRE(c_real >= 1 && c_real <= d->C && s_real >= 1 && s_real <= d->S, SSIP_ERR_ARG, "bad c_real/s_real");
-  {
-    HaloPlan hp;
-    if (stem_wg_plan(d, dtype, hp)) {
-      if (max_workgroups > 0) hp.G = std::min(hp.G, max_workgroups);
-      const int64_t sneed = (int64_t)hp.G * 64 * 224 * 4;
-      SSIP_REQUIRE(workspace_bytes >= sneed, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
-                   (long long)workspace_bytes, (long long)sneed);
-      StemWgArgs h;
-      h.X = static_cast<const __bf16*>(x);
-      h.DY = static_cast<const __bf16*>(dy);
-      h.slab = static_cast<float*>(workspace);
-      h.x_bytes = (uint32_t)((long)d->N * d->H * d->W * 8);
-      h.dy_bytes = (uint32_t)((long)d->N * d->P * d->Q * 64 * 2);
-      h.N = d->N; h.H = d->H; h.W = d->W; h.P = d->P; h.Q = d->Q; h.tiles = hp.tiles;
-      hipStream_t st = (hipStream_t)stream;
-      SSIP_KLAUNCH(conv_stem_wgrad_kernel, dim3(hp.G), dim3(512), 0, st, h);
-      rc = ::ssip::check_launch("conv_stem_wgrad");
-      if (rc) return rc;
-      const long total4 = 64L * 224 / 4;
-      int lg = 0;
-      while (lg < 6 && (2 << lg) <= hp.G && ((total4 << (lg + 1)) + 255) / 256 <= 1024) ++lg;
-      const long blocks = (total4 + (256 >> lg) - 1) / (256 >> lg);
-      SSIP_KLAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace,
-                         hp.G, 64, 224, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate, lg);
-      return ::ssip::check_launch("wgrad_reduce");
-    }
-    if (halo_wg_plan(d, dtype, hp))
-      return launch_halo_wgrad(d, hp, dy, x, dw_kcrs, c_real, s_real, accumulate, workspace, workspace_bytes,
-                               max_workgroups, (hipStream_t)stream, nullptr, nullptr);
-  }
-  return wgrad_implicit(pl, d, dtype, dy, x, dw_kcrs, c_real, s_real, accumulate, workspace, (hipStream_t)stream);
-}
-
-// the split-K implicit-GEMM wgrad of a planned conv + its fixed-order slab
-// reduce (ssip_conv_wgrad_budget; ssip_conv_wgrad_bnrelu_in with in_scale set)
-static int wgrad_implicit(Plan& pl, const ssip_conv_desc* d, int dtype, const void* dy, const void* x,
-                          float* dw_kcrs, int c_real, int s_real, int accumulate, void* workspace, hipStream_t st) {
-  int rc;
-  pl.args.A = dy; pl.args.B = x; pl.args.out = workspace;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->P * d->Q * d->K * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->N * d->H * d->W * d->C * 2);
-  {
-    const int PQ = d->P * d->Q, BKr = 64;  // LDS-DMA k-step rows (bf16)
-    const int dn = BKr / PQ, rem = BKr % PQ;
-    ConvArgs& g = pl.args;
-    g.wg_dn = dn;
-    g.wg_dp = rem / d->Q;
-    g.wg_dq = rem % d->Q;
-    g.wg_k0 = (dn * d->H * d->W + g.wg_dp * d->stride * d->W + g.wg_dq * d->stride) * d->C * 2;
-    g.wg_e1 = (d->stride * d->W - d->Q * d->stride) * d->C * 2;
-    g.wg_e2 = (d->H * d->W - d->P * d->stride * d->W) * d->C * 2;
-  }
-  SSIP_DISPATCH_DTYPE(dtype, T, rc = launch_conv<MODE_WGRAD, T>(pl, st));
-  if (rc) return rc;
-  const int RS = d->R * d->S;
-  if (c_real == d->C && s_real == d->S && d->C % 64 == 0 && RS <= WGR_T_MAXRS && pl.args.Ng == RS * d->C &&
-      pl.splits <= 32 && (long)d->K * (d->C / 64) >= 256 && (reinterpret_cast<uintptr_t>(dw_kcrs) & 15) == 0) {
-    SSIP_KLAUNCH(wgrad_reduce_t_kernel, dim3((unsigned)(d->K * (d->C / 64))), dim3(256), 0, st,
-                       (const float*)workspace, pl.splits, d->K, pl.args.Ng, d->C, RS, dw_kcrs, accumulate);
-    return ::ssip::check_launch("wgrad_reduce_t");
-  }
-  const long total4 = (long)d->K * pl.args.Ng / 4;  // Ng = R*S*C: C % 32 == 0, or the stem's 7x8x4
-  int lg = 0;  // split groups: double while splits allow and the grid stays within ~1024 workgroups
-  while (lg < 6 && (2 << lg) <= pl.splits && ((total4 << (lg + 1)) + 255) / 256 <= 1024) ++lg;
-  const long blocks = (total4 + (256 >> lg) - 1) / (256 >> lg);
-  SSIP_KLAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace,
-                     pl.splits, d->K, pl.args.Ng, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate, lg);
-  return ::ssip::check_launch("wgrad_reduce");
+  if (r.kind == ROUTE_STEM_WGRAD)
+    return launch_stem_wgrad(d, r.hp, dy, x, dw_kcrs, c_real, s_real, accumulate, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+  if (r.kind == ROUTE_HALO_WGRAD)
+    return launch_halo_wgrad(d, r.hp, dy, x, dw_kcrs, c_real, s_real, accumulate, workspace, workspace_bytes,
+                             (hipStream_t)stream, nullptr, nullptr);
+  return wgrad_implicit(r.pl, d, dtype, dy, x, dw_kcrs, c_real, s_real, accumulate, workspace, (hipStream_t)stream);
 }
 
 int ssip_stem_bwd_wgrad_supported(const ssip_conv_desc* d, int dtype) {
-  HaloPlan hp;
-  return (stem_wg_plan(d, dtype, hp) && d->Q * 2 == 224 && d->P % 2 == 0) ? 1 : 0;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  return stem_bwd_route(k, d, dtype, r) ? 1 : 0;
 }
 
 int ssip_stem_bwd_wgrad(const ssip_conv_desc* d, int dtype, const void* dpool, const uint8_t* idx, const void* y,
                         const void* x, const float* scale, const float* shift, const float* coef, float* dw_kcrs,
                         int c_real, int s_real, int accumulate, void* workspace, int64_t workspace_bytes,
                         void* stream) {
-  HaloPlan hp;
-  SSIP_REQUIRE(ssip_stem_bwd_wgrad_supported(d, dtype) && stem_wg_plan(d, dtype, hp), SSIP_ERR_ARG,
-               "ssip_stem_bwd_wgrad: unsupported geometry");
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  SSIP_REQUIRE(stem_bwd_route(k, d, dtype, r), SSIP_ERR_ARG, "ssip_stem_bwd_wgrad: unsupported geometry");
   SSIP_REQUIRE(dpool && idx && y && x && scale && shift && coef && dw_kcrs && workspace, SSIP_ERR_ARG,
                "ssip_stem_bwd_wgrad: null pointer");
   SSIP_REQUIRE(c_real >= 1 && c_real <= d->C && s_real >= 1 && s_real <= d->S, SSIP_ERR_ARG, "bad c_real/s_real");
-  const int64_t need = (int64_t)hp.G * 64 * 224 * 4;
+  const HaloPlan& hp = r.hp;
+  const int64_t need = persistent_slab_bytes(hp);
   SSIP_REQUIRE(workspace_bytes >= need, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
                (long long)workspace_bytes, (long long)need);
   const int P2 = (d->P + 2 - 3) / 2 + 1, Q2 = (d->Q + 2 - 3) / 2 + 1;  // the 3x3 / 2 / 1 max-pool
@@ -4143,63 +4164,54 @@ int ssip_stem_bwd_wgrad(const ssip_conv_desc* d, int dtype, const void* dpool, c
   h.N = d->N; h.H = d->H; h.W = d->W; h.P = d->P; h.Q = d->Q; h.P2 = P2; h.Q2 = Q2; h.tiles = hp.tiles;
   hipStream_t st = (hipStream_t)stream;
   SSIP_KLAUNCH(conv_stem_bwd_wgrad2_kernel, dim3(hp.G), dim3(768), 0, st, h);
-  int rc = ::ssip::check_launch("conv_stem_bwd_wgrad");
-  if (rc) return rc;
-  const long total4 = 64L * 224 / 4;
-  int lg = 0;
-  while (lg < 6 && (2 << lg) <= hp.G && ((total4 << (lg + 1)) + 255) / 256 <= 1024) ++lg;
-  const long blocks = (total4 + (256 >> lg) - 1) / (256 >> lg);
-  SSIP_KLAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace, hp.G,
-                     64, 224, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate, lg);
-  return ::ssip::check_launch("wgrad_reduce");
+  if (int rc = ::ssip::check_launch("conv_stem_bwd_wgrad")) return rc;
+  return launch_slab_reduce(workspace, hp.G, 64, hp.cols, c_real, d->R, s_real, d->C, d->S, dw_kcrs, accumulate, st);
 }
 
-
 int ssip_conv_bnrelu_in_supported(const ssip_conv_desc* d, int dtype) {
-  HaloPlan hp, hw;
-  if (halo_plan(MODE_FWD, d, dtype, hp) && halo_wg_plan(d, dtype, hw)) return 1;
-  Plan pf, pw;
-  return (glds_inbn_plan(MODE_FWD, d, dtype, pf) && glds_inbn_plan(MODE_WGRAD, d, dtype, pw)) ? 1 : 0;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute rf, rw;
+  return bnrelu_in_routes(k, d, dtype, rf, rw) ? 1 : 0;
 }
 
 int ssip_conv_fwd_bnrelu_in(const ssip_conv_desc* d, int dtype, const void* y_in, const float* in_scale,
                             const float* in_shift, const void* w_krsc, void* y, float* bn_partial, void* z_out,
                             void* stream) {
-  HaloPlan hp;
-  SSIP_REQUIRE(ssip_conv_bnrelu_in_supported(d, dtype), SSIP_ERR_ARG,
+  const ConvKnobs k = conv_knobs();
+  ConvRoute rf, rw;
+  SSIP_REQUIRE(bnrelu_in_routes(k, d, dtype, rf, rw), SSIP_ERR_ARG,
                "ssip_conv_fwd_bnrelu_in: unsupported geometry (ssip_conv_bnrelu_in_supported)");
   SSIP_REQUIRE(y_in && in_scale && in_shift && w_krsc && y, SSIP_ERR_ARG, "ssip_conv_fwd_bnrelu_in: null pointer");
-  if (halo_plan(MODE_FWD, d, dtype, hp))
-    return launch_halo(MODE_FWD, d, hp, y_in, w_krsc, y, nullptr, bn_partial, (hipStream_t)stream, nullptr, 0,
+  if (rf.kind == ROUTE_HALO)
+    return launch_halo(MODE_FWD, d, rf.hp, y_in, w_krsc, y, nullptr, bn_partial, (hipStream_t)stream, nullptr, 0,
                        nullptr, in_scale, in_shift, z_out);
-  Plan pl;
-  SSIP_REQUIRE(glds_inbn_plan(MODE_FWD, d, dtype, pl), SSIP_ERR_ARG,
-               "ssip_conv_fwd_bnrelu_in: no LDS-DMA BN+ReLU-in plan");
   SSIP_REQUIRE(z_out == nullptr || (d->R == 1 && d->S == 1 && d->pad == 0), SSIP_ERR_ARG,
                "ssip_conv_fwd_bnrelu_in: z_out on the halo geometry and 1x1 convs only");
-  pl.args.zout = z_out;
-  pl.args.A = y_in; pl.args.B = w_krsc; pl.args.out = y; pl.args.partial = bn_partial;
-  pl.args.a_bytes = (uint32_t)((long)d->N * d->H * d->W * d->C * 2);
-  pl.args.b_bytes = (uint32_t)((long)d->K * d->R * d->S * d->C * 2);
-  pl.args.in_scale = in_scale; pl.args.in_shift = in_shift;
-  return launch_glds<MODE_FWD>(pl, (hipStream_t)stream);
+  ConvArgs& a = rf.pl.args;  // the INBN ring plan
+  set_operands(a, d, MODE_FWD, y_in, w_krsc);
+  a.out = y; a.partial = bn_partial; a.zout = z_out;
+  a.in_scale = in_scale; a.in_shift = in_shift;
+  return launch_glds(rf.pl, (hipStream_t)stream);
 }
 
 int ssip_conv_wgrad_bnrelu_in(const ssip_conv_desc* d, int dtype, const void* dy, const void* y_in,
                               const float* in_scale, const float* in_shift, float* dw_kcrs, int accumulate,
                               void* workspace, int64_t workspace_bytes, int max_workgroups, void* stream) {
-  HaloPlan hp;
-  SSIP_REQUIRE(ssip_conv_bnrelu_in_supported(d, dtype), SSIP_ERR_ARG,
+  const ConvKnobs k = conv_knobs();
+  ConvRoute rf, rw;
+  SSIP_REQUIRE(bnrelu_in_routes(k, d, dtype, rf, rw), SSIP_ERR_ARG,
                "ssip_conv_wgrad_bnrelu_in: unsupported geometry (ssip_conv_bnrelu_in_supported)");
   SSIP_REQUIRE(dy && y_in && in_scale && in_shift && dw_kcrs && workspace && max_workgroups >= 0, SSIP_ERR_ARG,
                "ssip_conv_wgrad_bnrelu_in: bad arguments");
-  if (halo_wg_plan(d, dtype, hp))
-    return launch_halo_wgrad(d, hp, dy, y_in, dw_kcrs, d->C, d->S, accumulate, workspace, workspace_bytes,
-                             max_workgroups, (hipStream_t)stream, in_scale, in_shift);
-  Plan pl;
-  SSIP_REQUIRE(glds_inbn_plan(MODE_WGRAD, d, dtype, pl, max_workgroups), SSIP_ERR_ARG,
+  if (rw.kind == ROUTE_HALO_WGRAD) {
+    route_wgrad(k, d, dtype, max_workgroups, rw);  // the grid under this budget
+    return launch_halo_wgrad(d, rw.hp, dy, y_in, dw_kcrs, d->C, d->S, accumulate, workspace, workspace_bytes,
+                             (hipStream_t)stream, in_scale, in_shift);
+  }
+  Plan& pl = rw.pl;
+  SSIP_REQUIRE(glds_inbn_plan(k, MODE_WGRAD, d, dtype, pl, max_workgroups), SSIP_ERR_ARG,
                "ssip_conv_wgrad_bnrelu_in: no LDS-DMA BN+ReLU-in plan under this budget");
-  const int64_t need = (int64_t)pl.splits * pl.args.M * pl.args.Ng * 4;
+  const int64_t need = implicit_slab_bytes(pl);
   SSIP_REQUIRE(workspace_bytes >= need, SSIP_ERR_WORKSPACE, "wgrad workspace too small: %lld < %lld",
                (long long)workspace_bytes, (long long)need);
   pl.args.in_scale = in_scale; pl.args.in_shift = in_shift;
@@ -4212,45 +4224,31 @@ int ssip_conv_kernel_name(int mode, const ssip_conv_desc* d, int dtype, char* bu
   return ssip_conv_kernel_name_budget(mode, d, dtype, 0, buf, buflen);
 }
 
+// formats the route of the pass: no choice of its own
 int ssip_conv_kernel_name_budget(int mode, const ssip_conv_desc* d, int dtype, int max_workgroups, char* buf,
                                  int buflen) {
   SSIP_REQUIRE(buf && buflen > 0, SSIP_ERR_ARG, "ssip_conv_kernel_name: no buffer");
   SSIP_REQUIRE(max_workgroups >= 0, SSIP_ERR_ARG, "ssip_conv_kernel_name_budget: negative budget");
   SSIP_REQUIRE(mode >= 0 && mode <= 2, SSIP_ERR_ARG, "ssip_conv_kernel_name: mode must be 0 (fwd), 1 (dgrad), 2 (wgrad)");
-  static const char* mname[3] = {"fwd", "dgrad", "wgrad"};
-  const int m = mode == 0 ? MODE_FWD : mode == 1 ? MODE_DGRAD : MODE_WGRAD;
-  HaloPlan hp;
-  if (m == MODE_FWD && halo_plan(MODE_FWD, d, dtype, hp)) {
-    snprintf(buf, buflen, "halo<fwd,TR=%d,G=%d>", hp.TR, hp.G);
-    return SSIP_OK;
+  const ConvKnobs k = conv_knobs();
+  ConvRoute r;
+  const int rc = mode == MODE_FWD     ? route_fwd(k, d, dtype, r)
+                 : mode == MODE_DGRAD ? route_dgrad(k, d, dtype, r)
+                                      : route_wgrad(k, d, dtype, max_workgroups, r);
+  const Plan& pl = r.pl;
+  switch (r.kind) {
+    case ROUTE_HALO: snprintf(buf, buflen, "halo<%s,TR=%d,G=%d>", MODE_NAME[mode], r.hp.TR, r.hp.G); break;
+    case ROUTE_STEM: snprintf(buf, buflen, "stem_halo<fwd,G=%d>", r.hp.G); break;
+    case ROUTE_STEM_WGRAD: snprintf(buf, buflen, "stem_wgrad<G=%d>", r.hp.G); break;
+    case ROUTE_HALO_WGRAD: snprintf(buf, buflen, "halo_wgrad<TR=%d,G=%d>", r.hp.TR, r.hp.G); break;
+    case ROUTE_GLDS:
+    case ROUTE_REGSTAGED:
+      snprintf(buf, buflen, "%s<%s,%dx%d,%dx%d,%d%s%s,splits=%d>", r.kind == ROUTE_GLDS ? "glds" : "regstaged",
+               MODE_NAME[mode], pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages, pl.conv1 ? ",stem" : "",
+               pl.args.phased ? ",phased" : "", pl.splits);
+      break;
+    default: return rc;
   }
-  if (m == MODE_FWD && stem_plan(d, dtype, hp)) {
-    snprintf(buf, buflen, "stem_halo<fwd,G=%d>", hp.G);
-    return SSIP_OK;
-  }
-  if (m == MODE_DGRAD && halo_plan(MODE_DGRAD, d, dtype, hp)) {
-    snprintf(buf, buflen, "halo<dgrad,TR=%d,G=%d>", hp.TR, hp.G);
-    return SSIP_OK;
-  }
-  if (m == MODE_WGRAD && stem_wg_plan(d, dtype, hp)) {
-    snprintf(buf, buflen, "stem_wgrad<G=%d>", max_workgroups > 0 ? std::min(hp.G, max_workgroups) : hp.G);
-    return SSIP_OK;
-  }
-  if (m == MODE_WGRAD && halo_wg_plan(d, dtype, hp)) {
-    snprintf(buf, buflen, "halo_wgrad<TR=%d,G=%d>", hp.TR, max_workgroups > 0 ? std::min(hp.G, max_workgroups) : hp.G);
-    return SSIP_OK;
-  }
-  Plan pl;
-  int rc = plan_conv(m, d, elem_bytes_of(dtype), pl, m == MODE_WGRAD ? max_workgroups : 0);
-  if (rc) return rc;
-  if (m == MODE_FWD && pl.stages > 0 && !pl.conv1 && d->R * d->S > 32) fallback_regstaged(pl);
-  if (m == MODE_DGRAD) {
-    phase_split(pl, d);
-    if (pl.stages > 0 && ((d->stride != 1 && !pl.args.phased) || d->R * d->S > 32)) fallback_regstaged(pl);
-  }
-  snprintf(buf, buflen, "%s<%s,%dx%d,%dx%d,%d%s%s,splits=%d>", pl.stages > 0 ? "glds" : "regstaged", mname[mode],
-           pl.bm, pl.bn, pl.wmw, pl.wnw, pl.stages, pl.conv1 ? ",stem" : "", pl.args.phased ? ",phased" : "",
-           pl.splits);
   return SSIP_OK;
 }
 
