@@ -24,7 +24,8 @@
  *   (build extension, no reference) weak/strong consistency loss
  *     -> ssip_semi_loss
  *   KMeans / DBSCAN / silhouette_score / kneighbors   src/clustering.py:330-438
- *     -> ssip_kmeans_assign / _update, ssip_pairwise_eps / _kth / _cluster_sums
+ *     -> ssip_kmeans_assign / _update, ssip_pairwise_eps / _kth / _cluster_sums,
+ *        ssip_pairwise_degree + ssip_dbscan_walk / _hook (DBSCAN above 65,536 points)
  *   TSNE(...).fit_transform                  src/clustering.py:251-276
  *     -> ssip_tsne_cond_p / _joint_p / _grad / _update (the exact objective)
  *   umap.UMAP(...).fit_transform             src/clustering.py:279-306
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define SSIP_ABI_VERSION 17
+#define SSIP_ABI_VERSION 18
 
 enum ssip_dtype { SSIP_F32 = 0, SSIP_BF16 = 1 };
 enum ssip_status { SSIP_OK = 0, SSIP_ERR_ARG = -1, SSIP_ERR_LAUNCH = -2, SSIP_ERR_WORKSPACE = -3 };
@@ -404,8 +405,9 @@ int ssip_counters_add(int count, int64_t* const* ptrs, int64_t delta, void* stre
  * :330-337, evaluate_kmeans :340-373, evaluate_dbscan :376-428,
  * auto_eps_from_kdistance :430-438).  Points X are fp32 row-major [N][d],
  * 1 <= d <= 512.  Every squared distance is sum_c (x_c - y_c)^2 in fp32, one
- * fma per feature in feature order; no atomics, every reduction in a fixed
- * order (bit-reproducible).
+ * fma per feature in feature order; no atomics except the integer atomicMin
+ * of ssip_dbscan_hook (order-independent), every reduction in a fixed order
+ * (bit-reproducible).
  * ---------------------------------------------------------------------- */
 /* bytes of the Lloyd-iteration workspace: per-workgroup partial sums
  * [G][K][d], counts [G][K], inertia [G] and changed-label counts [G] */
@@ -429,6 +431,36 @@ int ssip_kmeans_update(int64_t N, int d, int K, const void* workspace, int64_t w
  * included), bitmap[i][j / 32] bit (j % 32) = the predicate, [N][ceil(N/32)]
  * uint32 with zero padding bits.  N <= 65536 (512 MB of bitmap). */
 int ssip_pairwise_eps(int N, int d, const float* X, float eps, int32_t* degree, uint32_t* bitmap, void* stream);
+/* DBSCAN without the bitmap, 1 <= N <= 2^20: the eps graph is never stored,
+ * cluster labels are propagated over distances recomputed by the same column
+ * walk and the same predicate as ssip_pairwise_eps, so the pair set is the
+ * bitmap's bit for bit.  One round is a walk and a hook for 1 <= M <= 4
+ * min_samples configurations at once; labels, nbr_min and scratch are int32
+ * [M][N], min_samples int32 [M] (device).  Row i is core in configuration m
+ * iff degree[i] >= min_samples[m].  Labels start as labels[m][i] = i on core
+ * rows and N (the sentinel) elsewhere; the host repeats walk + hook until
+ * changed is all zero, and the last walk's nbr_min then holds, for every row,
+ * the lowest core index of the cluster it belongs to (N = noise).  A label or
+ * minimum outside 0..N-1 is never used as an index: it is skipped.
+ *
+ * ssip_pairwise_degree: degree[i] as ssip_pairwise_eps computes it. */
+int ssip_pairwise_degree(int N, int d, const float* X, float eps, int32_t* degree, void* stream);
+/* nbr_min[m][i] = min of labels[m][j] over the core columns j of
+ * configuration m with d2(i, j) <= eps^2 (a core row's own label included),
+ * N when there is none; every row i, core or not.  nbr_min must not alias
+ * labels. */
+int ssip_dbscan_walk(int N, int d, const float* X, float eps, int M, const int32_t* degree,
+                     const int32_t* min_samples, const int32_t* labels, int32_t* nbr_min, void* stream);
+/* labels_out = labels_in; for every core row i, labels_out[labels_in[i]] and
+ * labels_out[i] are lowered to nbr_min[i]; then max(1, ceil(log2 N)) pointer
+ * jumps labels_out[i] = labels_out[labels_out[i]] on core rows, alternating
+ * between labels_out and scratch.  changed[m] = 1 when labels_out differs
+ * from labels_in anywhere in configuration m, else 0.  The lowering is the
+ * section's one atomic, an integer atomicMin, whose result does not depend on
+ * the order of arrival.  labels_out and scratch must not alias labels_in,
+ * nbr_min or each other. */
+int ssip_dbscan_hook(int N, int M, const int32_t* degree, const int32_t* min_samples, const int32_t* labels_in,
+                     const int32_t* nbr_min, int32_t* labels_out, int32_t* scratch, int32_t* changed, void* stream);
 /* kth[i] = k-th smallest distance (not squared) from row i to any row, self
  * included at 0: NearestNeighbors(n_neighbors=k).kneighbors(X)[0][:, -1].
  * 1 <= k <= min(64, N). */

@@ -1,5 +1,6 @@
 // Embedding analytics on the PCA cluster space: K-Means (Lloyd assign /
-// update), the DBSCAN eps-neighbourhood graph, the k-th neighbour distance
+// update), the DBSCAN eps-neighbourhood graph, DBSCAN label propagation
+// without a stored graph (degree / walk / hook), the k-th neighbour distance
 // and the per-cluster distance sums behind the silhouette score.  These stand
 // in for the sklearn calls the reference makes at src/clustering.py:330-438
 // (KMeans.fit_predict, DBSCAN.fit_predict, silhouette_score,
@@ -19,9 +20,13 @@
 // nothing.  The direct form also gives d2(i, j) == d2(j, i) and d2(i, i) == 0
 // bit for bit, so the eps graph is symmetric by construction.
 //
-// No atomics; every reduction runs in a fixed order, so all outputs are
-// bit-reproducible from run to run.  Two thread layouts:
-//   A (eps graph, k-th distance, exact kNN; the t-SNE distances of tsne.hip):
+// No atomics, with one exception: the DBSCAN hook takes an integer atomicMin
+// on the label array.  A minimum of integers does not depend on the order of
+// arrival, so that output is as reproducible as the rest; there are no
+// floating-point atomics.  Every other reduction runs in a fixed order, so all
+// outputs are bit-reproducible from run to run.  Two thread layouts:
+//   A (eps graph and degree, DBSCAN walk, k-th distance, exact kNN; the t-SNE
+//     distances of tsne.hip):
 //     a workgroup owns RA = 64 rows and walks all columns in tiles of 64
 //     (pairwise_tile.h); lane = column, each wave holds 16 rows, so one wave
 //     ballot is 64 columns of one row = two bitmap words.  The k-th distance
@@ -43,11 +48,14 @@ constexpr int UPD_NT = 1024;  // update: one workgroup
 
 constexpr int KNN_MAX_N = 1 << 20;
 constexpr int KNN_MAX_K = 64;
+constexpr int DBSCAN_MAX_N = 1 << 20;
+constexpr int DBSCAN_MAX_M = 4;  // min_samples configurations of one walk
 
 // ---------------------------------------------------------------------------
 // layout A (the walk and the selection are pairwise_tile.h's)
 // ---------------------------------------------------------------------------
-// degree + adjacency bitmap of d2 <= eps2
+// degree and (BITMAP) adjacency bitmap of d2 <= eps2
+template <bool BITMAP>
 __global__ __launch_bounds__(NT) void pairwise_eps_kernel(int N, int d, const float* __restrict__ X, float eps2,
                                                           int* __restrict__ degree, uint32_t* __restrict__ bitmap) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -66,16 +74,115 @@ __global__ __launch_bounds__(NT) void pairwise_eps_kernel(int N, int d, const fl
       deg[u] += __popcll(m);
       if ((lane >> 1) == u) mine = m;
     }
-    // lanes 0..31 store the wave's 16 rows x 2 words
-    const int i = row0 + w * 16 + (lane >> 1), wi = jt * 2 + (lane & 1);
-    if (lane < 32 && i < N && wi < W)
-      bitmap[(long)i * W + wi] = (uint32_t)((lane & 1) ? (mine >> 32) : (mine & 0xffffffffull));
+    if constexpr (BITMAP) {
+      // lanes 0..31 store the wave's 16 rows x 2 words
+      const int i = row0 + w * 16 + (lane >> 1), wi = jt * 2 + (lane & 1);
+      if (lane < 32 && i < N && wi < W)
+        bitmap[(long)i * W + wi] = (uint32_t)((lane & 1) ? (mine >> 32) : (mine & 0xffffffffull));
+    }
   });
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
     const int i = row0 + w * 16 + u;
     if (lane == u && i < N) degree[i] = deg[u];
   }
+}
+
+// One DBSCAN label walk for M min_samples configurations over one tile of
+// d2: nbr_min[m][i] = min of labels[m][j] over the columns j that are core in
+// configuration m (degree[j] >= min_samples[m]) and have d2(i, j) <= eps2, N
+// when there is none.  The predicate is pairwise_eps_kernel's, so the pair set
+// is the bitmap's bit for bit.  lane = column: the lane fetches its column's
+// degree and M labels once per tile and keeps a running minimum per (m, row);
+// the 64 lanes of a row are reduced once, after the walk.  A label outside
+// 0..N-1 counts as N.
+template <int M>
+__global__ __launch_bounds__(NT) void dbscan_walk_kernel(int N, int d, const float* __restrict__ X, float eps2,
+                                                         const int* __restrict__ degree,
+                                                         const int* __restrict__ min_samples,
+                                                         const int* __restrict__ labels, int* __restrict__ nbr_min) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * RA;
+  int ms[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) ms[m] = min_samples[m];
+  int mn[M][16];
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int u = 0; u < 16; ++u) mn[m][u] = N;
+  walk_columns_a(N, d, X, row0, [&](int jt, const float(&acc)[16]) {
+    const int j = jt * 64 + lane;
+    const int dj = j < N ? degree[j] : 0;
+    int cl[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) cl[m] = j < N ? labels[(long)m * N + j] : N;
+    unsigned hits = 0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = row0 + w * 16 + u;
+      hits |= (unsigned)(j < N && i < N && acc[u] <= eps2) << u;
+    }
+    if (!__any(hits != 0)) return;  // wave-uniform: no pair of this tile is within eps
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      if (dj < ms[m] || (unsigned)cl[m] >= (unsigned)N) cl[m] = N;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) mn[m][u] = min(mn[m][u], ((hits >> u) & 1u) ? cl[m] : N);
+    }
+  });
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      int v = mn[m][u];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+      const int i = row0 + w * 16 + u;
+      if (lane == u && i < N) nbr_min[(long)m * N + i] = v;
+    }
+  }
+}
+
+// The hook of one DBSCAN round, thread = (configuration m, row i) = idx / N,
+// idx % N.  copy: out = in, changed = 0.  min: every core row i hooks its
+// neighbourhood minimum onto itself and onto its current label's row.  jump:
+// dst[i] = src[src[i]] on core rows (Jacobi: src is read only, dst written
+// only); the last jump reports a difference from the round's input labels.  A
+// label or minimum outside 0..N-1 is never used as an index.
+constexpr int HOOK_NT = 256;
+__global__ __launch_bounds__(HOOK_NT) void dbscan_hook_copy_kernel(int N, int M, const int* __restrict__ in,
+                                                                   int* __restrict__ out, int* __restrict__ changed) {
+  const int idx = blockIdx.x * HOOK_NT + threadIdx.x;
+  if (idx < M * N) out[idx] = in[idx];
+  if (idx < M) changed[idx] = 0;
+}
+__global__ __launch_bounds__(HOOK_NT) void dbscan_hook_min_kernel(int N, int M, const int* __restrict__ degree,
+                                                                  const int* __restrict__ min_samples,
+                                                                  const int* __restrict__ in,
+                                                                  const int* __restrict__ nbr_min, int* out) {
+  const int idx = blockIdx.x * HOOK_NT + threadIdx.x;
+  if (idx >= M * N) return;
+  const int m = idx / N, i = idx - m * N;
+  if (degree[i] < min_samples[m]) return;
+  const int nm = nbr_min[idx], l = in[idx];
+  if ((unsigned)nm >= (unsigned)N) return;
+  if ((unsigned)l < (unsigned)N) atomicMin(&out[m * N + l], nm);
+  atomicMin(&out[idx], nm);
+}
+template <bool LAST>
+__global__ __launch_bounds__(HOOK_NT) void dbscan_hook_jump_kernel(int N, int M, const int* __restrict__ degree,
+                                                                   const int* __restrict__ min_samples,
+                                                                   const int* __restrict__ src, int* __restrict__ dst,
+                                                                   const int* __restrict__ in,
+                                                                   int* __restrict__ changed) {
+  const int idx = blockIdx.x * HOOK_NT + threadIdx.x;
+  if (idx >= M * N) return;
+  const int m = idx / N, i = idx - m * N;
+  int v = src[idx];
+  if (degree[i] >= min_samples[m] && (unsigned)v < (unsigned)N) v = src[m * N + v];
+  dst[idx] = v;
+  if (LAST && v != in[idx]) changed[m] = 1;  // every writer stores the same value
 }
 
 // k-th distance: the key is the squared distance alone
@@ -409,6 +516,13 @@ __global__ __launch_bounds__(NT) void cluster_sums_kernel(int N, int d, int K, c
   if (cur >= 0 && row < N) sums[row * K + cur] = run;
 }
 
+// true when two int32 [M][N] arrays share a byte
+inline bool dbscan_overlap(const void* p, const void* q, long N, int M) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  const uintptr_t bytes = (uintptr_t)N * M * sizeof(int32_t);
+  return a < b + bytes && b < a + bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -452,9 +566,73 @@ int ssip_pairwise_eps(int N, int d, const float* X, float eps, int32_t* degree, 
                "ssip_pairwise_eps: N = %d above 65536 (the adjacency bitmap would exceed 512 MB)", N);
   SSIP_REQUIRE(eps >= 0.f, SSIP_ERR_ARG, "ssip_pairwise_eps: eps = %g must be >= 0", (double)eps);
   SSIP_REQUIRE(degree && bitmap, SSIP_ERR_ARG, "ssip_pairwise_eps: null pointer");
-  SSIP_KLAUNCH(pairwise_eps_kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps,
+  SSIP_KLAUNCH(pairwise_eps_kernel<true>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps,
                degree, bitmap);
   return ssip::check_launch("ssip_pairwise_eps");
+}
+
+int ssip_pairwise_degree(int N, int d, const float* X, float eps, int32_t* degree, void* stream) {
+  if (int rc = check_points("ssip_pairwise_degree", N, d, X)) return rc;
+  SSIP_REQUIRE(N <= DBSCAN_MAX_N, SSIP_ERR_ARG, "ssip_pairwise_degree: N = %d above %d", N, DBSCAN_MAX_N);
+  SSIP_REQUIRE(eps >= 0.f, SSIP_ERR_ARG, "ssip_pairwise_degree: eps = %g must be >= 0", (double)eps);
+  SSIP_REQUIRE(degree != nullptr, SSIP_ERR_ARG, "ssip_pairwise_degree: null pointer");
+  SSIP_KLAUNCH(pairwise_eps_kernel<false>, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X,
+               eps * eps, degree, (uint32_t*)nullptr);
+  return ssip::check_launch("ssip_pairwise_degree");
+}
+
+int ssip_dbscan_walk(int N, int d, const float* X, float eps, int M, const int32_t* degree, const int32_t* min_samples,
+                     const int32_t* labels, int32_t* nbr_min, void* stream) {
+  if (int rc = check_points("ssip_dbscan_walk", N, d, X)) return rc;
+  SSIP_REQUIRE(N <= DBSCAN_MAX_N, SSIP_ERR_ARG, "ssip_dbscan_walk: N = %d above %d", N, DBSCAN_MAX_N);
+  SSIP_REQUIRE(eps >= 0.f, SSIP_ERR_ARG, "ssip_dbscan_walk: eps = %g must be >= 0", (double)eps);
+  SSIP_REQUIRE(M >= 1 && M <= DBSCAN_MAX_M, SSIP_ERR_ARG, "ssip_dbscan_walk: M = %d outside 1..%d", M, DBSCAN_MAX_M);
+  SSIP_REQUIRE(degree && min_samples && labels && nbr_min, SSIP_ERR_ARG, "ssip_dbscan_walk: null pointer");
+  SSIP_REQUIRE(!dbscan_overlap(labels, nbr_min, N, M), SSIP_ERR_ARG,
+               "ssip_dbscan_walk: nbr_min must not alias labels");
+  auto kernel = dbscan_walk_kernel<1>;  // one instance per M: the minima live in registers
+  if (M == 2) kernel = dbscan_walk_kernel<2>;
+  if (M == 3) kernel = dbscan_walk_kernel<3>;
+  if (M == 4) kernel = dbscan_walk_kernel<4>;
+  SSIP_KLAUNCH(kernel, dim3((N + RA - 1) / RA), dim3(NT), 0, (hipStream_t)stream, N, d, X, eps * eps, degree,
+               min_samples, labels, nbr_min);
+  return ssip::check_launch("ssip_dbscan_walk");
+}
+
+int ssip_dbscan_hook(int N, int M, const int32_t* degree, const int32_t* min_samples, const int32_t* labels_in,
+                     const int32_t* nbr_min, int32_t* labels_out, int32_t* scratch, int32_t* changed, void* stream) {
+  SSIP_REQUIRE(N >= 1 && N <= DBSCAN_MAX_N, SSIP_ERR_ARG, "ssip_dbscan_hook: N = %d outside 1..%d", N, DBSCAN_MAX_N);
+  SSIP_REQUIRE(M >= 1 && M <= DBSCAN_MAX_M, SSIP_ERR_ARG, "ssip_dbscan_hook: M = %d outside 1..%d", M, DBSCAN_MAX_M);
+  SSIP_REQUIRE(degree && min_samples && labels_in && nbr_min && labels_out && scratch && changed, SSIP_ERR_ARG,
+               "ssip_dbscan_hook: null pointer");
+  SSIP_REQUIRE(!dbscan_overlap(labels_in, labels_out, N, M) && !dbscan_overlap(labels_in, scratch, N, M) &&
+                   !dbscan_overlap(labels_out, scratch, N, M) && !dbscan_overlap(nbr_min, labels_out, N, M) &&
+                   !dbscan_overlap(nbr_min, scratch, N, M),
+               SSIP_ERR_ARG,
+               "ssip_dbscan_hook: labels_out and scratch must not alias labels_in, nbr_min or each other");
+  // ceil(log2 N) jumps (at least one, which carries the comparison) halve
+  // every chain of decreasing labels down to its root.  They alternate
+  // between two buffers, started so that the last one writes labels_out.
+  int jumps = 0;
+  while ((1L << jumps) < N) ++jumps;
+  if (jumps < 1) jumps = 1;
+  int* a = (jumps % 2 == 0) ? labels_out : scratch;
+  int* b = (jumps % 2 == 0) ? scratch : labels_out;
+  const dim3 grid((M * N + HOOK_NT - 1) / HOOK_NT), block(HOOK_NT);
+  const hipStream_t st = (hipStream_t)stream;
+  SSIP_KLAUNCH(dbscan_hook_copy_kernel, grid, block, 0, st, N, M, labels_in, a, changed);
+  SSIP_KLAUNCH(dbscan_hook_min_kernel, grid, block, 0, st, N, M, degree, min_samples, labels_in, nbr_min, a);
+  for (int k = 0; k < jumps; ++k) {
+    const int* src = (k % 2 == 0) ? a : b;
+    int* dst = (k % 2 == 0) ? b : a;
+    if (k == jumps - 1)
+      SSIP_KLAUNCH(dbscan_hook_jump_kernel<true>, grid, block, 0, st, N, M, degree, min_samples, src, dst, labels_in,
+                   changed);
+    else
+      SSIP_KLAUNCH(dbscan_hook_jump_kernel<false>, grid, block, 0, st, N, M, degree, min_samples, src, dst, labels_in,
+                   changed);
+  }
+  return ssip::check_launch("ssip_dbscan_hook");
 }
 
 int ssip_pairwise_kth(int N, int d, int k, const float* X, float* kth, void* stream) {

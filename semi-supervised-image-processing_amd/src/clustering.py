@@ -19,6 +19,10 @@ What runs where:
     ``--device cuda`` (and ``auto``) uses the HIP kernels; ``--device cpu`` is
     an explicit host path on the same driver with the numpy backend.  Two
     extension flags: ``--device``, ``--tsne-method`` and ``--umap-method``.
+    DBSCAN takes up to 2^20 rows: up to 65,536 it labels a packed eps graph on
+    the host, above that it propagates labels on the backend without storing
+    the graph (ssip.analytics.dbscan_sweep picks by the row count; the labels
+    are the same).
   * Standardisation checks and PCA (sklearn, svd_solver="full": the reference's
     cluster space bit for bit) stay on the host: O(N*D^2) at most, against
     O(N^2*d) per DBSCAN / silhouette configuration.
@@ -300,18 +304,19 @@ def evaluate_dbscan(space: EmbeddingResult, bundle: FeatureBundle, eps_values: S
                     min_samples_values: Sequence[int], seed: int, scope: str = "all", device: str = "cuda",
                     backend=None) -> List[ClusteringResult]:
     """DBSCAN over the grids on the scope's subset; points outside it are -1
-    and the silhouette is taken on the fitted subset (:384-389).  The eps graph
-    is built once per eps and labelled for every min_samples."""
+    and the silhouette is taken on the fitted subset (:384-389).  Every
+    min_samples of one eps is labelled in one analytics.dbscan_sweep: from one
+    eps graph up to analytics.EPS_MAX_N rows, by label propagation without a
+    stored graph above that."""
     mask = bundle.scope_mask(scope)
     sub = space.data[mask]
     if backend is None or scope != "all":
         backend = analytics.make_backend(sub, device)
     out = []
     for eps in eps_values:
-        degree, bitmap = backend.eps_graph(float(eps))
-        for ms in min_samples_values:
-            logging.info("Fitting DBSCAN (scope=%s) with eps=%.3f, min_samples=%s", scope, eps, ms)
-            sub_labels = analytics.dbscan_labels_from_graph(degree, bitmap, int(ms))
+        logging.info("Fitting DBSCAN (scope=%s) with eps=%.3f, min_samples=%s", scope, eps, list(min_samples_values))
+        sweep = analytics.dbscan_sweep(backend, float(eps), [int(ms) for ms in min_samples_values])
+        for ms, sub_labels in zip(min_samples_values, sweep):
             full = np.full(space.data.shape[0], -1, dtype=int)
             full[mask] = sub_labels
             ari, nmi = compute_external_metrics(bundle, full)

@@ -29,7 +29,7 @@ def abi_version_expected() -> int:
     return int(m.group(1)) if m else ABI_VERSION
 
 
-ABI_VERSION = 17  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
+ABI_VERSION = 18  # must equal include/ssip.h SSIP_ABI_VERSION (tests/test_cpu_abi.py)
 
 F32 = 0
 BF16 = 1
@@ -142,6 +142,9 @@ _SIGS = {
     "ssip_kmeans_assign": (_c_int, [_c_i64, _c_int, _c_int] + [_vp] * 6 + [_c_i64, _vp]),
     "ssip_kmeans_update": (_c_int, [_c_i64, _c_int, _c_int, _vp, _c_i64] + [_vp] * 5),
     "ssip_pairwise_eps": (_c_int, [_c_int, _c_int, _vp, _c_f, _vp, _vp, _vp]),
+    "ssip_pairwise_degree": (_c_int, [_c_int, _c_int, _vp, _c_f, _vp, _vp]),
+    "ssip_dbscan_walk": (_c_int, [_c_int, _c_int, _vp, _c_f, _c_int] + [_vp] * 5),
+    "ssip_dbscan_hook": (_c_int, [_c_int, _c_int] + [_vp] * 8),
     "ssip_pairwise_kth": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "ssip_pairwise_cluster_sums": (_c_int, [_c_int, _c_int, _c_int] + [_vp] * 5),
     # exact t-SNE (ssip/analytics.py)

@@ -14,7 +14,11 @@ csrc/analytics.hip; what stays on the host is the control flow around them:
 * ``dbscan`` labels by sklearn's order-free rule: cluster ids are the
   connected components of the core-point graph numbered by their lowest core
   index, a border point takes the smallest id among its core neighbours,
-  everything else is -1.
+  everything else is -1.  Up to ``EPS_MAX_N`` points the eps graph is a packed
+  bitmap labelled breadth-first on the host; above it (``dbscan_stream``, to
+  ``DBSCAN_STREAM_MAX_N``) no graph is stored: labels are propagated on the
+  backend over recomputed distances, a walk and a hook per round with one
+  read-back of the ``changed`` flags, for up to four min_samples at once.
 * ``silhouette`` finishes a, b and s in fp64 from per-cluster distance sums.
 * ``tsne_fit`` is sklearn's exact t-SNE (``TSNE(method="exact", init="pca",
   learning_rate="auto")``): the joint probabilities once (csrc/tsne.hip), then
@@ -44,6 +48,9 @@ MAX_ITER = 300
 TOL = 1e-4
 KTH_MAX = 64
 EPS_MAX_N = 65536
+DBSCAN_STREAM_MAX_N = 1 << 20
+DBSCAN_STREAM_MAX_M = 4  # min_samples configurations of one walk
+DBSCAN_MAX_WALKS = 64
 SILHOUETTE_MAX_K = 256
 TSNE_MAX_N = 32768  # P is N^2 floats: 4 GB at the cap (csrc/tsne.hip)
 TSNE_EXPLORATION_ITERS = 250
@@ -108,6 +115,21 @@ def dbscan_labels_from_graph(degree: np.ndarray, bitmap: np.ndarray, min_samples
         labels[take] = cid
         cid += 1
     return labels
+
+
+def _dbscan_min_samples(values) -> np.ndarray:
+    """int32 [M] min_samples of one walk, 1 <= M <= DBSCAN_STREAM_MAX_M."""
+    ms = np.minimum(np.asarray(list(values), dtype=np.int64).reshape(-1), np.iinfo(np.int32).max).astype(np.int32)
+    if not 1 <= ms.size <= DBSCAN_STREAM_MAX_M:
+        raise ValueError(f"ssip.analytics: a DBSCAN walk takes 1..{DBSCAN_STREAM_MAX_M} min_samples values "
+                         f"(got {ms.size})")
+    return ms
+
+
+def _dbscan_init_labels(degree: np.ndarray, ms: np.ndarray) -> np.ndarray:
+    """int32 [M][N]: a core row starts as its own label, every other row holds the sentinel N."""
+    n = degree.shape[0]
+    return np.where(degree[None, :] >= ms[:, None], np.arange(n, dtype=np.int32)[None, :], np.int32(n)).astype(np.int32)
 
 
 def _relocate_empty(X: np.ndarray, labels: np.ndarray, mind2: np.ndarray, old: np.ndarray) -> np.ndarray:
@@ -222,6 +244,55 @@ class NumpyBackend:
             degree[s:e] = adj.sum(axis=1)
             bitmap[s:e] = pack_adjacency(adj)
         return degree, bitmap
+
+    # DBSCAN without the bitmap (dbscan_stream): the predicate of eps_graph in
+    # row blocks, O(block x N) memory.
+    def degree(self, eps: float) -> np.ndarray:
+        from scipy.spatial.distance import cdist
+
+        self._db_e2 = float(eps) * float(eps)
+        self._db_degree = np.zeros(self.n, dtype=np.int32)
+        for s, e in self._row_chunks(self.n):
+            self._db_degree[s:e] = (cdist(self.X[s:e], self.X, "sqeuclidean") <= self._db_e2).sum(axis=1)
+        return self._db_degree.copy()
+
+    def dbscan_begin(self, min_samples_values) -> None:
+        """Start the label problems of the last ``degree(eps)``, one per min_samples."""
+        self._db_ms = _dbscan_min_samples(min_samples_values)
+        self._db_labels = _dbscan_init_labels(self._db_degree, self._db_ms)
+        self._db_nbr = np.full_like(self._db_labels, self.n)
+
+    def dbscan_walk(self) -> None:
+        """nbr_min[m][i] = min label over the core columns within eps of row i (N: none)."""
+        from scipy.spatial.distance import cdist
+
+        n = self.n
+        core = self._db_degree[None, :] >= self._db_ms[:, None]
+        col = np.where(core, self._db_labels, n)
+        for s, e in self._row_chunks(n):
+            adj = cdist(self.X[s:e], self.X, "sqeuclidean") <= self._db_e2
+            for m in range(self._db_ms.size):
+                self._db_nbr[m, s:e] = np.where(adj, col[m][None, :], n).min(axis=1)
+
+    def dbscan_hook(self) -> np.ndarray:
+        """Hook every core row's minimum onto itself and its label's row, then
+        max(1, ceil(log2 N)) pointer jumps; returns changed[m]."""
+        n = self.n
+        changed = np.zeros(self._db_ms.size, dtype=np.int32)
+        for m in range(self._db_ms.size):
+            old, nbr = self._db_labels[m], self._db_nbr[m]
+            rows = np.flatnonzero((self._db_degree >= self._db_ms[m]) & (nbr < n))
+            new = old.copy()
+            np.minimum.at(new, old[rows], nbr[rows])
+            new[rows] = np.minimum(new[rows], nbr[rows])
+            for _ in range(max(1, (n - 1).bit_length())):
+                new[rows] = new[new[rows]]
+            changed[m] = int(np.any(new != old))
+            self._db_labels[m] = new
+        return changed
+
+    def dbscan_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self._db_labels.copy(), self._db_nbr.copy()
 
     def kth(self, k: int) -> np.ndarray:
         from scipy.spatial.distance import cdist
@@ -563,6 +634,44 @@ class DeviceBackend:
                    self._p(bitmap))
         return degree.cpu().numpy(), bitmap.cpu().numpy().view(np.uint32)
 
+    # DBSCAN without the bitmap (dbscan_stream): degree, labels and minima stay
+    # on the device; a round reads back the changed flags only.
+    def degree(self, eps: float) -> np.ndarray:
+        t = self._torch
+        if self.n > DBSCAN_STREAM_MAX_N:
+            raise ValueError(f"ssip.analytics: DBSCAN supports N <= {DBSCAN_STREAM_MAX_N} (got {self.n})")
+        self._db_eps = float(eps)
+        self._db_degree = t.empty(self.n, dtype=t.int32, device=self.dev)
+        self._call("ssip_pairwise_degree", self.n, self.d, self._p(self.X), self._db_eps, self._p(self._db_degree))
+        self._db_degree_host = self._db_degree.cpu().numpy()
+        return self._db_degree_host.copy()
+
+    def dbscan_begin(self, min_samples_values) -> None:
+        """Start the label problems of the last ``degree(eps)``, one per min_samples."""
+        t = self._torch
+        ms = _dbscan_min_samples(min_samples_values)
+        self._db_m = int(ms.size)
+        self._db_ms = t.from_numpy(ms).to(self.dev)
+        self._db_labels = t.from_numpy(_dbscan_init_labels(self._db_degree_host, ms)).to(self.dev)
+        self._db_next = t.empty_like(self._db_labels)
+        self._db_scratch = t.empty_like(self._db_labels)
+        self._db_nbr = t.full_like(self._db_labels, self.n)
+        self._db_changed = t.empty(self._db_m, dtype=t.int32, device=self.dev)
+
+    def dbscan_walk(self) -> None:
+        self._call("ssip_dbscan_walk", self.n, self.d, self._p(self.X), self._db_eps, self._db_m,
+                   self._p(self._db_degree), self._p(self._db_ms), self._p(self._db_labels), self._p(self._db_nbr))
+
+    def dbscan_hook(self) -> np.ndarray:
+        self._call("ssip_dbscan_hook", self.n, self._db_m, self._p(self._db_degree), self._p(self._db_ms),
+                   self._p(self._db_labels), self._p(self._db_nbr), self._p(self._db_next),
+                   self._p(self._db_scratch), self._p(self._db_changed))
+        self._db_labels, self._db_next = self._db_next, self._db_labels
+        return self._db_changed.cpu().numpy()  # the one read-back of a round
+
+    def dbscan_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self._db_labels.cpu().numpy(), self._db_nbr.cpu().numpy()
+
     def kth(self, k: int) -> np.ndarray:
         t = self._torch
         out = t.empty(self.n, dtype=t.float32, device=self.dev)
@@ -772,11 +881,66 @@ def kmeans_fit(X: np.ndarray, k: int, n_init: int = 10, seed: int = 42, device: 
     return labels.astype(np.int32), float(inertia), centres + mean
 
 
+def dbscan_stream(backend, eps: float, min_samples_values):
+    """DBSCAN labels without a stored eps graph: (one int64 label array per
+    min_samples value, the walks each of them took).
+
+    Per chunk of up to ``DBSCAN_STREAM_MAX_M`` values, which share every tile
+    of distances: a core row starts as its own label; a walk gives every row
+    the smallest label among the core points within eps; the hook lowers every
+    core row and the row its label names to that minimum and then jumps every
+    core row to the label of its label, so a component collapses onto its
+    lowest core index in O(log) rounds, not O(diameter).  The walk that changes
+    nothing already holds, for every row, core or border, the lowest core index
+    of the smallest-numbered cluster it touches (N = noise); ranking those
+    roots numbers the clusters by their lowest core index.  The same labels as
+    ``dbscan_labels_from_graph`` on the same backend's eps graph."""
+    n = backend.n
+    if n > DBSCAN_STREAM_MAX_N:
+        raise ValueError(f"ssip.analytics: DBSCAN supports N <= {DBSCAN_STREAM_MAX_N} (got {n})")
+    values = [int(v) for v in min_samples_values]
+    degree = backend.degree(float(eps))
+    labels, walks = [], []
+    for c in range(0, len(values), DBSCAN_STREAM_MAX_M):
+        chunk = values[c:c + DBSCAN_STREAM_MAX_M]
+        backend.dbscan_begin(chunk)
+        settled = [0] * len(chunk)  # the first walk after which a configuration did not change
+        for walk in range(1, DBSCAN_MAX_WALKS + 1):
+            backend.dbscan_walk()
+            changed = backend.dbscan_hook()
+            for m in range(len(chunk)):
+                if not changed[m] and not settled[m]:
+                    settled[m] = walk
+            if not np.any(changed):
+                break
+        else:
+            raise RuntimeError(f"ssip.analytics: DBSCAN labels still changing after {DBSCAN_MAX_WALKS} walks "
+                               f"(N = {n}, eps = {eps}, min_samples = {chunk})")
+        final, nbr_min = backend.dbscan_state()
+        for m, ms in enumerate(chunk):
+            roots = np.unique(final[m][degree >= ms])
+            near = np.asarray(nbr_min[m], dtype=np.int64)
+            labels.append(np.where(near < n, np.searchsorted(roots, near), -1).astype(np.int64))
+        walks += settled
+    return labels, walks
+
+
+def dbscan_sweep(backend, eps: float, min_samples_values) -> list:
+    """DBSCAN labels at one eps for every min_samples value (a list of int64
+    arrays).  Up to ``EPS_MAX_N`` points: the eps graph once, labelled per
+    value on the host.  Above it: ``dbscan_stream``."""
+    if backend.n > DBSCAN_STREAM_MAX_N:
+        raise ValueError(f"ssip.analytics: DBSCAN supports N <= {DBSCAN_STREAM_MAX_N} (got {backend.n})")
+    if backend.n <= EPS_MAX_N:
+        degree, bitmap = backend.eps_graph(float(eps))
+        return [dbscan_labels_from_graph(degree, bitmap, int(ms)) for ms in min_samples_values]
+    return dbscan_stream(backend, float(eps), min_samples_values)[0]
+
+
 def dbscan(X: np.ndarray, eps: float, min_samples: int, device: str = "cuda", backend=None) -> np.ndarray:
     """Labels of sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(X)."""
     backend = backend if backend is not None else make_backend(X, device)
-    degree, bitmap = backend.eps_graph(float(eps))
-    return dbscan_labels_from_graph(degree, bitmap, int(min_samples))
+    return dbscan_sweep(backend, float(eps), [int(min_samples)])[0]
 
 
 def silhouette(X: np.ndarray, labels: np.ndarray, device: str = "cuda", backend=None) -> float:
